@@ -1,8 +1,16 @@
 """bench.py -- inner-loop steps/sec of the MAML adaptation path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up (W steps), times K steps and prints ONE JSON line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step) and the configuration.  Everything else it
+can report (below) is measured with --full only.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (run_train_iter: the meta-batch
+loss, the other logged losses, each task's prediction) as DIR/<name>.npy in float32 / float64.  Inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs[1]): SepConv, meta-batch 4 tasks per GPU, 5 inner steps, synthetic
 256x448x3 septuplets, LSLR + SGD inner rule, L1 loss, outer Adam -- seeded random-init weights.
@@ -11,7 +19,8 @@ One "step" of this script = one run_train_iter over the rank's meta-batch (4 tas
 `value` = inner-loop steps/sec summed over all ranks (weak scaling: 4 tasks per GPU), measured in the PRODUCT DEFAULT
 mode (config.py: the rank's tasks adapted in lockstep, eager autograd, one stream).
 
-The line also carries
+With --full the line also carries
+  value_reading_the_loss_every_iteration: the K timed steps again, the loss read (one host sync) after every step;
   roofline     : the dominant custom kernel (sepconv backward, gV+gH) -- algorithmic bytes per launch
                  (4*[B*3*(Ho+50)(Wo+50) + 4*B*51*Ho*Wo + B*3*Ho*Wo]) / mean launch time from HIP events
                  recorded on the launch stream INSIDE the timed region (single stream: nothing shares the GPU with a
@@ -24,7 +33,12 @@ The line also carries
                  backward);
   parity_check : that same oracle sample against the TIMED system in the TIMED mode: theta restored to the seeded weights, the
                  outer step disabled, one more meta-iteration over the same meta-batch (tasks in lockstep), task 0's
-                 prediction / loss / PSNR against the oracle's.
+                 prediction / loss / PSNR against the oracle's;
+  strong_c4    : SepConv C2 runs only: BASELINE config 4 at a fixed global meta-batch of 32 tasks, timed and checked against
+                 the reference-generated fixture.
+--fast-path (with or without --full) adds `fast_path`: the same workload from hipGraph replays on four task streams.
+--full keeps roofline, roofline_mfma, cpu_baseline and strong_c4 switchable off by --no-kernel-timer, --no-cpu-baseline and
+--no-strong-c4.
 """
 import argparse
 import json
@@ -211,6 +225,40 @@ def c4_parity_eval(res, fix, world):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, losses, preds):
+    """What one run_train_iter returned to its caller, as out_dir/<name>.npy: every numeric entry of the losses dict under its own
+    key (`loss`: the meta-batch loss; float64) and `pred_task<t>` for each task this rank adapted (the prediction as returned,
+    [1,3,H,W] in 0..1; float32).  Should the predictions pass 64 MB in all, each is cut to the same fixed, seeded sample of its
+    flattened elements (numpy default_rng(0), sorted indices).  Returns the names written."""
+    import re
+    import numpy as np
+    arrays = {}
+    for k, v in losses.items():        # (a lazy losses dict waits here for the step's logging)
+        if torch.is_tensor(v):
+            v = v.detach().double().cpu().numpy()
+        try:
+            arrays[re.sub(r'[^A-Za-z0-9_.-]', '_', str(k))] = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            continue
+    small = sum(a.nbytes for a in arrays.values())
+    big = {'pred_task%d' % t: p.detach().float().cpu().numpy() for t, p in enumerate(preds) if torch.is_tensor(p)}
+    total = sum(a.nbytes for a in big.values())
+    room = DUMP_BYTES - small - 256 * (len(arrays) + len(big))       # (.npy headers)
+    if total > room:
+        frac = room / total
+        for name, a in big.items():
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            big[name] = a.reshape(-1)[idx]
+    arrays.update(big)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def _from_unit_range(system, img01):
     """Inverse of SceneAdaptiveInterpolation._to_unit_range (predictions are returned in 0..1; the loss lives in the plugin's range)."""
     if system.args.model == 'voxelflow':
@@ -226,6 +274,11 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='c2_sepconv_256x448_b4_s5', choices=sorted(WORKLOADS))
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline: the loss-reading repeat of the timed steps, roofline '
+                         '(HIP events inside the timed region), roofline_mfma, cpu_baseline + parity_check, strong_c4')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (losses, per-task predictions) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timer', action='store_true')
     # product switches: None = the default of meta-interpolation_amd/config.py
@@ -245,6 +298,8 @@ def main():
                     help='FIXED global meta-batch (strong scaling: tasks/GPU = global / gpus, e.g. 32 for BASELINE config 4); default: '
                          'the workload\'s tasks per GPU on every rank (weak scaling)')
     opt = ap.parse_args()
+    if opt.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     from meta_interpolation_amd import _hip, synthetic, task_parallel
     from meta_interpolation_amd.config import default_args
@@ -301,12 +356,13 @@ def main():
     frames = synthetic.septuplet_batch(tasks * world, H, W, model='sepconv' if toy else model)
     frames = [f.to(dev) for f in frames]                # inputs resident in HBM before the timed region
 
-    theta0 = {k: v.detach().clone() for k, v in system.state_dict().items()} if (rank == 0 and not toy) else None
+    theta0 = {k: v.detach().clone() for k, v in system.state_dict().items()} if (opt.full and rank == 0 and not toy) else None
 
-    def one_iter(it, read_loss=False):
-        losses, _, _ = system.run_train_iter(data_batch=frames, epoch=0, do_evaluation=False)
+    def one_iter(it, read_loss=False, keep=False):
+        losses, preds, _ = system.run_train_iter(data_batch=frames, epoch=0, do_evaluation=False)
         if read_loss:       # what a training loop that logs every iteration does (experiment_builder.py:58-74): a host sync per iteration
             float(losses['loss'])
+        return (losses, preds) if keep else None
 
     for i in range(opt.warmup):
         one_iter(i)
@@ -317,7 +373,7 @@ def main():
     HBM_KERNELS = {'sepconv': ('sepconv',), 'voxelflow': ('voxelwarp', 'mt_update'), 'cain': ('pixel_', 'mt_update', 'ca_'),
                    'rrin': ('flowwarp', 'mt_update'), 'superslomo': ('flowwarp', 'mt_update')}
     timer = None
-    if not opt.no_kernel_timer and model == 'sepconv':
+    if opt.full and not opt.no_kernel_timer and model == 'sepconv':
         timer = _hip.KernelTimer(only=HBM_KERNELS[model])
         _hip.TIMER = timer
     tp.record_timing = tp.active and dev.type == 'cuda'
@@ -325,29 +381,36 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(opt.steps):
-        one_iter(i)
+        last = one_iter(i, keep=i == opt.steps - 1)
     sync()
     tp.barrier()
     elapsed = time.perf_counter() - t0
     _hip.TIMER = None
     tp.record_timing = False
     ar_stats = tp.allreduce_stats()
-    # the same K iterations again with the loss READ every iteration (the returned dicts fetch their numbers on first read: a caller
-    # that logs every iteration syncs once per iteration, exactly where the reference's run_train_iter does; `value` is the product's
-    # default behaviour for a caller that does not read)
-    tp.barrier()
-    sync()
-    t1 = time.perf_counter()
-    for i in range(opt.steps):
-        one_iter(i, read_loss=True)
-    sync()
-    tp.barrier()
-    elapsed_logged = time.perf_counter() - t1
-    if tp.active:
-        import torch.distributed as dist
-        t = torch.tensor([elapsed_logged], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed_logged = float(t.item())
+    if opt.dump_outputs and rank == 0:
+        # before anything else runs: graph replays write their outputs into buffers a later replay reuses
+        names = dump_outputs(opt.dump_outputs, *last)
+        print("[bench] last timed step's outputs -> %s: %s" % (opt.dump_outputs, " ".join(names)), file=sys.stderr)
+    del last
+    elapsed_logged = None
+    if opt.full:
+        # the same K iterations again with the loss READ every iteration (the returned dicts fetch their numbers on first read: a caller
+        # that logs every iteration syncs once per iteration, exactly where the reference's run_train_iter does; `value` is the product's
+        # default behaviour for a caller that does not read)
+        tp.barrier()
+        sync()
+        t1 = time.perf_counter()
+        for i in range(opt.steps):
+            one_iter(i, read_loss=True)
+        sync()
+        tp.barrier()
+        elapsed_logged = time.perf_counter() - t1
+        if tp.active:
+            import torch.distributed as dist
+            t = torch.tensor([elapsed_logged], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed_logged = float(t.item())
     # the replicas took the same optimizer steps from the same theta: bit-identical parameters on every rank (no broadcast anywhere)
     replicas_ok = tp.replicas_identical([p for p in system.parameters()]) if tp.active else None
     if tp.active:
@@ -363,7 +426,6 @@ def main():
         "metric": "inner-loop steps/sec", "value": inner_steps / elapsed, "unit": "inner-loop steps/sec",
         "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": 1e3 * elapsed / opt.steps,
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "value_reading_the_loss_every_iteration": tasks * world * S * opt.steps / elapsed_logged,
         # fp32 arithmetic end to end; the direct convolution kernels evaluate every fp32 product as six bf16 products of exactly
         # split operands with fp32 accumulation (csrc/convk.hip: as close to float64 as an fp32 fmaf chain)
         # the 51-tap op on frames of 8-bit images (k / 255, classified on the device at every call): the frame operand is the exact integer k
@@ -378,6 +440,8 @@ def main():
                    "parallelism": "task-parallel x%d, 1 all-reduce of outer grads" % world, "mode": mode,
                    "outer_tasks_per_sec": tasks * world * opt.steps / elapsed},
     }
+    if elapsed_logged is not None:
+        line["value_reading_the_loss_every_iteration"] = tasks * world * S * opt.steps / elapsed_logged
     if tp.active:
         import torch.distributed as dist
         backend = dist.get_backend()
@@ -442,7 +506,7 @@ def main():
                         "algorithmic_bytes_per_launch": k["algorithmic_bytes"] / k["launches"],
                         "note": "largest HBM-bound savfi kernel of this workload by time; launches of a few microseconds are "
                                 "latency-bound, not bandwidth-bound (see `kernels` for the others)"}
-        if world == 1 and not toy and dev.type == 'cuda' and not opt.no_kernel_timer:
+        if opt.full and world == 1 and not toy and dev.type == 'cuda' and not opt.no_kernel_timer:
             # ONE extra meta-iteration of the timed system with HIP events around every convolution launch (outside the timed
             # region: ~600 event records per iteration would sit between the kernels of `value`).  Where the timed mode replays
             # hipGraphs (single-task ranks: C1, C5) a kernel cannot be timed in place: the extra iteration runs the same workload
@@ -522,7 +586,7 @@ def main():
                 del fsys, fnet
             except Exception as e:
                 line["fast_path"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-        if world == 1 and not opt.no_cpu_baseline and not toy:
+        if opt.full and world == 1 and not opt.no_cpu_baseline and not toy:
             line["cpu_baseline"], oracle_res = cpu_baseline(model, H, W, S, over_all)
             try:
                 line["parity_check"] = parity_check(system, theta0, frames, model, H, W, S, oracle_res, dev, mode,
@@ -532,7 +596,7 @@ def main():
     tp.barrier()
     # BASELINE config 4 at its FIXED global meta-batch (32 tasks: strong scaling -- 32 / gpus tasks per rank), every rank count incl. 1,
     # so that outer-gradient throughput at N GPUs can be set against 1 GPU on the same total work (north star: >= 6x at 8)
-    if model == 'sepconv' and not toy and not opt.no_strong_c4 and not opt.global_batch and 32 % world == 0 and opt.workload.startswith('c2_'):
+    if opt.full and model == 'sepconv' and not toy and not opt.no_strong_c4 and not opt.global_batch and 32 % world == 0 and opt.workload.startswith('c2_'):
         c4_model, c4H, c4W, _, c4S, c4over = WORKLOADS['c4_sepconv_msl_256x448_b4_s5']
         # the configuration of the reference-generated 32-task fixture (tests/golden/full_c4b32_*.npz: MAML++ multi-step loss AND learnable
         # per-layer per-step learning rates, inner_lr 1e-3), so that the timed system is the one `parity_check` holds to the reference

@@ -10,6 +10,7 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
@@ -59,7 +60,8 @@ def build_library(force=False, verbose=True):
     # library travels with the snapshot), then one link
     hipcc = find_hipcc()
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"] + ["-I", os.path.join(REPO_DIR, "include"), "-I", CSRC]
-    cache = os.environ.get("SAVFI_BUILD_CACHE", "/tmp/savfi_build_cache")
+    # per user: a cache directory another account created is not writable here
+    cache = os.environ.get("SAVFI_BUILD_CACHE") or os.path.join(tempfile.gettempdir(), "savfi_build_cache-%d" % os.getuid())
     os.makedirs(cache, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [os.path.join(REPO_DIR, "include", "savfi_hip.h")]
     hh = hashlib.sha256()

@@ -4,8 +4,8 @@ R=$GRAFT_REPO_ROOT
 A=$R/gpurun_out/art5; rm -rf $A; mkdir -p $A
 cd $R
 V=$R/tools/scratch/variants
-T0=$(date +%s); python bench.py > $A/r05_bench_line.json 2> $A/r05_bench_line.err; T1=$(date +%s); echo "python bench.py (default flags): wall $((T1 - T0)) s" > $A/r05_bench_default_run_time.txt
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-strong-c4"
+T0=$(date +%s); python bench.py --full > $A/r05_bench_line.json 2> $A/r05_bench_line.err; T1=$(date +%s); echo "python bench.py --full: wall $((T1 - T0)) s" > $A/r05_bench_default_run_time.txt
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-strong-c4"
 tag() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); d['config']['mode']['sepconv']=sys.argv[1]; print(json.dumps(d))" "$1"; }
 # the ladder on this box
 SAVFI_SEPCONV_PAIR_TWO_LAUNCHES=1 $B 2>/dev/null | tag "two launches per pass (SAVFI_SEPCONV_PAIR_TWO_LAUNCHES=1)" > $A/r05_pair_ab.jsonl
@@ -16,7 +16,7 @@ SAVFI_NO_CONV_CHAIN=1 $B 2>/dev/null | tag "default, every conv + ReLU with its 
 SAVFI_WGRAD3_NO_RING=1 $B 2>/dev/null | tag "default, 3x3 weight gradients routed as before the all-taps kernel (SAVFI_WGRAD3_NO_RING=1)" >> $A/r05_pair_ab.jsonl
 $B 2>/dev/null | tag "one launch per pass (default), again" >> $A/r05_pair_ab.jsonl
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-strong-c4 > $A/r05_bench_line_profiled.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-strong-c4 > $A/r05_bench_line_profiled.json 2>/dev/null
 python $R/tools/gap_report.py /tmp/prof_c2 0 > $A/r05_bench_c2_one_iteration.txt 2>&1
 f=$(find /tmp/prof_c2 -name "*kernel_stats.csv" | head -1); head -40 "$f" > $A/r05_bench_c2_kernel_stats.csv
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pmc_f -- python $R/tools/hbm_traffic.py run > /dev/null 2>&1
@@ -49,8 +49,8 @@ rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ
 python $R/tools/pmc_summary.py /tmp/pmcw2 wgrad >> $A/r05_pmc_wgrad3.txt 2>&1
 cd $R
 python tools/layer_table.py --workload c2_sepconv_256x448_b4_s5 --top 60 > $A/r05_layer_table_c2.txt 2>/dev/null
-SAVFI_WGRAD3_FORM=0 python bench.py --workload c5_cain_l2f_720p_b1_s1 --steps 3 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); d['config']['note']='3x3 weight gradients on the tap-split kernel (SAVFI_WGRAD3_FORM=0)'; print(json.dumps(d))" > $A/r05_c5_wgrad_ab.jsonl
-for w in c4_sepconv_msl_256x448_b4_s5 c3_voxelflow_metasgd_256x256_b8_s5 c5_cain_l2f_720p_b1_s1 rrin_256x448_b4_s5 superslomo_256x448_b4_s5 c1_cain_64x64_b1_s1; do python bench.py --workload $w --steps 3 --warmup 2 2>/dev/null >> $A/r05_other_configs.jsonl; done
+SAVFI_WGRAD3_FORM=0 python bench.py --full --workload c5_cain_l2f_720p_b1_s1 --steps 3 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); d['config']['note']='3x3 weight gradients on the tap-split kernel (SAVFI_WGRAD3_FORM=0)'; print(json.dumps(d))" > $A/r05_c5_wgrad_ab.jsonl
+for w in c4_sepconv_msl_256x448_b4_s5 c3_voxelflow_metasgd_256x256_b8_s5 c5_cain_l2f_720p_b1_s1 rrin_256x448_b4_s5 superslomo_256x448_b4_s5 c1_cain_64x64_b1_s1; do python bench.py --full --workload $w --steps 3 --warmup 2 2>/dev/null >> $A/r05_other_configs.jsonl; done
 python -m pytest tests -m gpu -q 2>&1 | tail -9 > $A/r05_pytest_gpu_tail.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $A/r05_smoke.txt 2>&1; tail -3 $A/r05_smoke.txt
 cat $A/r05_bench_line.json | cut -c1-1500; cat $A/r05_bench_default_run_time.txt; tail -3 $A/r05_pytest_gpu_tail.txt

@@ -6,9 +6,9 @@ A=$R/gpurun_out/art6; mkdir -p $A
 cd $R
 part=${1:-a}
 if [ "$part" = a ]; then
-T0=$(date +%s); timeout 600 python bench.py > $A/r06_bench_line.json 2> $A/r06_bench_line.err; T1=$(date +%s); echo "python bench.py (default flags): wall $((T1 - T0)) s" > $A/r06_bench_default_run_time.txt
+T0=$(date +%s); timeout 600 python bench.py --full > $A/r06_bench_line.json 2> $A/r06_bench_line.err; T1=$(date +%s); echo "python bench.py --full: wall $((T1 - T0)) s" > $A/r06_bench_default_run_time.txt
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-strong-c4 > $A/r06_bench_line_profiled.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-strong-c4 > $A/r06_bench_line_profiled.json 2>/dev/null
 python $R/tools/gap_report.py /tmp/prof_c2 0 > $A/r06_bench_c2_one_iteration.txt 2>&1
 f=$(find /tmp/prof_c2 -name "*kernel_stats.csv" | head -1); head -40 "$f" > $A/r06_bench_c2_kernel_stats.csv
 # HBM traffic of the roofline kernel (separate --pmc passes, the guide's corrections: tools/hbm_traffic.py)
@@ -36,9 +36,9 @@ python tools/layer_table.py --workload c5_cain_l2f_720p_b1_s1 --top 60 > $A/r06_
 
 fi
 if [ "$part" = c ]; then
-for w in c2script_sepconv_metasgd_adamax_256x448_b3_s3 c4_sepconv_msl_256x448_b4_s5 c3_voxelflow_metasgd_256x256_b8_s5 c5_cain_l2f_720p_b1_s1 rrin_256x448_b4_s5 superslomo_256x448_b4_s5 c1_cain_64x64_b1_s1; do timeout 400 python bench.py --workload $w --steps 3 --warmup 2 2>/dev/null >> $A/r06_other_configs.jsonl; done
+for w in c2script_sepconv_metasgd_adamax_256x448_b3_s3 c4_sepconv_msl_256x448_b4_s5 c3_voxelflow_metasgd_256x256_b8_s5 c5_cain_l2f_720p_b1_s1 rrin_256x448_b4_s5 superslomo_256x448_b4_s5 c1_cain_64x64_b1_s1; do timeout 400 python bench.py --full --workload $w --steps 3 --warmup 2 2>/dev/null >> $A/r06_other_configs.jsonl; done
 # two ranks on ONE GPU over gloo: the multi-rank GPU path of the final tree (the driver's 8-GPU run is the only RCCL run there is)
-SAVFI_DIST_BACKEND=gloo timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $A/r06_world2_one_gpu_gloo.json 2> $A/r06_world2_one_gpu_gloo.err
+SAVFI_DIST_BACKEND=gloo timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $A/r06_world2_one_gpu_gloo.json 2> $A/r06_world2_one_gpu_gloo.err
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -9 > $A/r06_pytest_gpu_tail.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $A/r06_smoke.txt 2>&1; tail -3 $A/r06_smoke.txt
 cat $A/r06_bench_line.json | cut -c1-1200; cat $A/r06_bench_default_run_time.txt; tail -3 $A/r06_pytest_gpu_tail.txt
