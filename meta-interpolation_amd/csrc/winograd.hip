@@ -782,6 +782,18 @@ extern "C" int64_t savfi_conv3x3_workspace_floats(int N, int Ci, int Co, int H, 
 
 namespace {
 
+// launches one wino4_conv3x3 instantiation; each has its own flag of the devices its 72 KB dynamic-LDS attribute is set on (one static
+// in a generic lambda shared by all instantiations -- they have one function type -- configured only the first one launched)
+template <int VECW, int IN16, bool MASK>
+int launch_wino4(const w4::W4Args& a4, int64_t wgs4, hipStream_t st) {
+  static uint32_t configured = 0;
+  constexpr size_t lds4 = (size_t)w4::LDS_FLOATS * sizeof(float);      // 72 KB: two workgroups per CU
+  auto kern = w4::wino4_conv3x3<VECW, IN16, MASK>;
+  if (int rc = savfi_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds4, configured)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)wgs4), dim3(256), lds4, st, a4);
+  return savfi_launch_status();
+}
+
 // launches wino_conv3x3 (+ the split reduction) on an already transformed filter U [T][16 * KP * IP]
 int launch_conv(const WinoPlan& p, const float* x, const float* U, const float* bias, float* out, float* partial, int N, int T,
                 int H, int W, int mode, float slope, hipStream_t st, const float* mask = nullptr, float mask_slope = 1.f,
@@ -792,28 +804,22 @@ int launch_conv(const WinoPlan& p, const float* x, const float* U, const float* 
     if (mask && (out_unit16 || in_unit16)) return SAVFI_E_UNSUPPORTED;
     if (p.nsplit > 1 && (out_unit16 || in_unit16 || !partial)) return SAVFI_E_UNSUPPORTED;
     if (in_unit16 && ((p.off != 1 && p.off != 2) || p.Wo % 2 != 0)) return SAVFI_E_UNSUPPORTED;
-    constexpr size_t lds4 = (size_t)w4::LDS_FLOATS * sizeof(float);      // 72 KB: two workgroups per CU
     w4::W4Args a4{x, U, (mode & 1) == 0 ? bias : nullptr, out, p.K, p.I, p.KP, p.IP, H, W, p.Ho, p.Wo, p.off, p.th, p.tw, slope,
                   p.tile_shift, T, N, p.nsplit > 1 ? nullptr : mask, mask_slope, out_unit16, p.nsplit, p.chunks_per_split, partial};
     const int vecw = p.Wo % 4 == 0 ? 4 : (p.Wo % 2 == 0 ? 2 : 1);
-    auto go = [&](auto kern) -> int {
-      static uint32_t configured = 0;
-      if (int rc = savfi_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds4, configured)) return rc;
-      hipLaunchKernelGGL(kern, dim3((unsigned)wgs4), dim3(256), lds4, st, a4);
-      return savfi_launch_status();
-    };
-    if (in_unit16 && p.off == 1) return vecw == 4 ? go(w4::wino4_conv3x3<4, 2, false>) : go(w4::wino4_conv3x3<2, 2, false>);
-    if (in_unit16) return vecw == 4 ? go(w4::wino4_conv3x3<4, 3, false>) : go(w4::wino4_conv3x3<2, 3, false>);
+    auto go = [&](auto kern) { return kern(a4, wgs4, st); };
+    if (in_unit16 && p.off == 1) return vecw == 4 ? go(launch_wino4<4, 2, false>) : go(launch_wino4<2, 2, false>);
+    if (in_unit16) return vecw == 4 ? go(launch_wino4<4, 3, false>) : go(launch_wino4<2, 3, false>);
     if (p.nsplit > 1) {
-      const int rc = vecw == 4 ? go(w4::wino4_conv3x3<4, 0, false>) : vecw == 2 ? go(w4::wino4_conv3x3<2, 0, false>) : go(w4::wino4_conv3x3<1, 0, false>);
+      const int rc = vecw == 4 ? go(launch_wino4<4, 0, false>) : vecw == 2 ? go(launch_wino4<2, 0, false>) : go(launch_wino4<1, 0, false>);
       if (rc != SAVFI_OK) return rc;
       const size_t total = (size_t)N * p.I * p.Ho * p.Wo;
       hipLaunchKernelGGL(wino_split_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, partial, (mode & 1) == 0 ? bias : nullptr, out,
                          p.nsplit, total, p.I, p.Ho * p.Wo, slope, T, mask, mask_slope);
       return savfi_launch_status();
     }
-    if (mask) return vecw == 4 ? go(w4::wino4_conv3x3<4, 0, true>) : vecw == 2 ? go(w4::wino4_conv3x3<2, 0, true>) : go(w4::wino4_conv3x3<1, 0, true>);
-    return vecw == 4 ? go(w4::wino4_conv3x3<4, 0, false>) : vecw == 2 ? go(w4::wino4_conv3x3<2, 0, false>) : go(w4::wino4_conv3x3<1, 0, false>);
+    if (mask) return vecw == 4 ? go(launch_wino4<4, 0, true>) : vecw == 2 ? go(launch_wino4<2, 0, true>) : go(launch_wino4<1, 0, true>);
+    return vecw == 4 ? go(launch_wino4<4, 0, false>) : vecw == 2 ? go(launch_wino4<2, 0, false>) : go(launch_wino4<1, 0, false>);
   }
   const int64_t wgs = (int64_t)p.th * p.tw * (p.IP / COB) * p.nsplit * N;
   if (wgs > 0x7fffffffLL || T > 65535) return SAVFI_E_TOOBIG;
