@@ -20,6 +20,7 @@
  *   savfi_mt_mean_f32          per-tensor mean of grads (L2F embedding) meta_learning_system.py:249-253
  *   savfi_mt_scale_f32         gamma_i * w_i (L2F attenuation)        meta_learning_system.py:267-268
  *   savfi_l1_mse_f32           nn.L1Loss / nn.MSELoss                 loss.py:287-290
+ *   savfi_ssim_loss_f32        pytorch_msssim.SSIM as Loss constructs it, forward and gradient   loss.py:294, pytorch_msssim/__init__.py:7-131
  *   savfi_upsample2x_fwd/bwd_f32  bilinear x2 up-sampling                 sepconv/model.py:191,213-234; voxel_flow.py:400-414
  *   savfi_upsample2x_window_fwd/bwd_f32  the same map on a window (SepConv Subnets on the frame area)  sepconv/model.py:309-349
  *   savfi_bias_act_fwd/bwd_f32 conv bias add + (Leaky)ReLU and their backward + bias gradient
@@ -56,7 +57,7 @@
 extern "C" {
 #endif
 
-#define SAVFI_ABI_VERSION 20
+#define SAVFI_ABI_VERSION 21
 
 #define SAVFI_OK            0
 #define SAVFI_E_NULL       (-1)  /* a required pointer is NULL                          */
@@ -276,6 +277,32 @@ int64_t savfi_l1_mse_scratch_floats(int rows, int64_t n);
 int savfi_l1_mse_f32(int kind, const float* a, const float* b, float* result, float* scratch, int rows, int64_t n, void* stream);
 int savfi_l1_mse_bwd_f32(int kind, const float* a, const float* b, const float* g_loss, float* g_a,
                          int rows, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Fused SSIM loss term and its gradient (csrc/ssim.hip), `rows` independent losses per launch:
+ *   sr, hr [rows, C, H, W] (prediction, target); result[r] = (1 - mean SSIM map of row r) / 2, the map being the 11 x 11
+ *   Gaussian-window (sigma 1.5), valid (unpadded) SSIM of pytorch_msssim: C (H - 10) (W - 10) values per row.
+ *   H, W >= 11, SAVFI_E_SHAPE otherwise; rows * C <= 65535 and H * W < 2^31, SAVFI_E_TOOBIG otherwise.
+ * The dynamic range L of C1 = (0.01 L)^2, C2 = (0.03 L)^2 is the reference's data-dependent rule, evaluated on the device
+ * (no host read: capturable): range class = (min(sr) < -0.5 ? 1 : 0) | (max(sr) > 128 ? 2 : 0), L = 1, 2, 255, 256.
+ *   range_mode SAVFI_SSIM_RANGE_PER_ROW   the rule on every row on its own (what `rows` calls on N = 1 tensors give)
+ *              SAVFI_SSIM_RANGE_BATCH     the rule and the mean over all rows: ONE loss (what one call on an N = rows tensor gives);
+ *                                         result, range_word and, in the backward, g_loss have one element, and the backward is
+ *                                         called with rows = 1 and C = rows * C
+ *              SAVFI_SSIM_RANGE_FIXED + k the class k = 0..3 whatever the data (k = 2: L = 255, the PSNR / SSIM metric)
+ *   range_word[r]: the class the forward took (fully overwritten); the backward reads it, nothing else is kept.
+ *   `scratch`: savfi_ssim_scratch_floats(rows, C, H, W) floats (per-workgroup partial sums added in a fixed order and partial
+ *   extrema: the value is bit-reproducible; no atomics).
+ *   bwd: g_sr [rows, C, H, W] = g_loss[r] * d result[r] / d sr (fully overwritten); the target gets no gradient.
+ * ---------------------------------------------------------------------------------- */
+#define SAVFI_SSIM_RANGE_PER_ROW 0
+#define SAVFI_SSIM_RANGE_BATCH   1
+#define SAVFI_SSIM_RANGE_FIXED   2
+int64_t savfi_ssim_scratch_floats(int rows, int C, int H, int W);
+int savfi_ssim_loss_f32(const float* sr, const float* hr, float* result, uint32_t* range_word, float* scratch, int rows, int C,
+                        int H, int W, int range_mode, void* stream);
+int savfi_ssim_loss_bwd_f32(const float* sr, const float* hr, const float* g_loss, const uint32_t* range_word, float* g_sr,
+                            int rows, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:

@@ -16,7 +16,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "savfi_hip.h")
 
 RULE_SGD, RULE_ADAM, RULE_ADAMAX_LSLR, RULE_ADAMAX_MSGD = 0, 1, 2, 3
 LR_SCALAR, LR_ELEMENT = 0, 1
-ABI_VERSION = 20
+SSIM_RANGE_PER_ROW, SSIM_RANGE_BATCH, SSIM_RANGE_FIXED = 0, 1, 2
+ABI_VERSION = 21
 
 _ERRORS = {-1: "SAVFI_E_NULL (a required pointer is NULL)",
            -2: "SAVFI_E_SHAPE (bad or inconsistent dimension)",
@@ -70,6 +71,9 @@ _PROTOTYPES = {
     "savfi_l1_mse_scratch_floats": [c_int, c_int64],
     "savfi_l1_mse_f32": [c_int, _P, _P, _P, _P, c_int, c_int64, _P],
     "savfi_l1_mse_bwd_f32": [c_int, _P, _P, _P, _P, c_int, c_int64, _P],
+    "savfi_ssim_scratch_floats": [c_int, c_int, c_int, c_int],
+    "savfi_ssim_loss_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "savfi_ssim_loss_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_fwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_bwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_workspace_floats": [c_int] * 7,

@@ -691,6 +691,102 @@ def mse_loss_per_sample(a, b):
 
 
 # --------------------------------------------------------------------------------------------
+# Fused SSIM loss term                      (loss.py:294 -> pytorch_msssim/__init__.py:7-131)
+# --------------------------------------------------------------------------------------------
+class _SsimLoss(torch.autograd.Function):
+    """sr, hr [N,C,H,W] -> float32[N] of (1 - mean SSIM) / 2 per sample (range rule per sample), or float32[1] over the whole
+    batch (range rule over the batch); the range class stays on the device (capturable); deterministic."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, mode):
+        _hip.require_cuda(sr, hr)
+        assert sr.dim() == 4 and sr.shape == hr.shape, (sr.shape, hr.shape)
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("ssim_loss differentiates w.r.t. the prediction only: on the reference's path the target is a "
+                                      "clone of a data frame (loss.py:340)")
+        N, C, H, W = sr.shape
+        out_rows = 1 if mode == _hip.SSIM_RANGE_BATCH else N
+        res = torch.empty(out_rows, dtype=torch.float32, device=sr.device)
+        word = torch.empty(out_rows, dtype=torch.int32, device=sr.device)
+        scratch = torch.empty(_workspace_floats("savfi_ssim_scratch_floats", N, C, H, W), dtype=torch.float32, device=sr.device)
+        lib = _hip.lib()
+        _hip.launch("ssim_loss", lambda: _hip.check(lib.savfi_ssim_loss_f32(
+            sr.data_ptr(), hr.data_ptr(), res.data_ptr(), word.data_ptr(), scratch.data_ptr(), N, C, H, W, mode,
+            _hip.current_stream()), "savfi_ssim_loss_f32"), nbytes=8 * sr.numel())
+        ctx.batch = mode == _hip.SSIM_RANGE_BATCH
+        ctx.save_for_backward(sr, hr, word)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        sr, hr, word = ctx.saved_tensors
+        N, C, H, W = sr.shape
+        rows, ch = (1, N * C) if ctx.batch else (N, C)      # one loss over the batch: the samples are further channel planes
+        g = g.contiguous()
+        gsr = torch.empty_like(sr)
+        lib = _hip.lib()
+        _hip.launch("ssim_loss_bwd", lambda: _hip.check(lib.savfi_ssim_loss_bwd_f32(
+            sr.data_ptr(), hr.data_ptr(), g.data_ptr(), word.data_ptr(), gsr.data_ptr(), rows, ch, H, W,
+            _hip.current_stream()), "savfi_ssim_loss_bwd_f32"), nbytes=12 * sr.numel())
+        return gsr, None, None
+
+
+@functools.lru_cache(maxsize=None)
+def _ssim_taps(device):
+    """The 11 fp32 window taps of pytorch_msssim.create_window on `device` (built once per device)."""
+    import math
+    g = torch.tensor([math.exp(-(x - 5) ** 2 / 4.5) for x in range(11)], dtype=torch.float32)
+    return (g / g.sum()).to(device)
+
+
+def _ssim_composed(sr, hr, per_sample):
+    """The same formula from differentiable device ops (what --second_order takes): separable 11-tap window, the range decided
+    by torch.where on device tensors (no host read)."""
+    C = sr.shape[1]
+    taps = _ssim_taps(sr.device)
+    wr, wc = taps.view(1, 1, 1, 11).expand(C, 1, 1, 11), taps.view(1, 1, 11, 1).expand(C, 1, 11, 1)
+
+    def win(x):
+        return torch.nn.functional.conv2d(torch.nn.functional.conv2d(x, wr, groups=C), wc, groups=C)
+    d = sr.detach()
+    hi, lo = (d.amax((1, 2, 3), keepdim=True), d.amin((1, 2, 3), keepdim=True)) if per_sample else (d.max(), d.min())
+    one = torch.ones_like(hi)
+    L = torch.where(hi > 128, 255 * one, one) + torch.where(lo < -0.5, one, 0 * one)
+    C1, C2 = (0.01 * L) ** 2, (0.03 * L) ** 2
+    mu1, mu2 = win(sr), win(hr)
+    s1, s2, s12 = win(sr * sr) - mu1 * mu1, win(hr * hr) - mu2 * mu2, win(sr * hr) - mu1 * mu2
+    smap = ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2))
+    return (1 - (smap.flatten(1).mean(1) if per_sample else smap.mean())) / 2
+
+
+def _ssim_args(sr, hr):
+    if sr.dim() != 4 or sr.shape != hr.shape or sr.shape[2] < 11 or sr.shape[3] < 11:
+        raise ValueError("ssim_loss needs two [N,C,H,W] tensors of one shape with H, W >= 11 (the window is always 11 wide), got %s, %s"
+                         % (tuple(sr.shape), tuple(hr.shape)))
+    sr, hr = sr.contiguous(), hr.contiguous()
+    _hip.require_cuda(sr, hr)
+    return sr, hr
+
+
+def ssim_loss(sr, hr):
+    """pytorch_msssim.SSIM() as the reference's Loss constructs and calls it (loss.py:294, :340): (1 - mean SSIM) / 2 over the
+    whole batch, dynamic range from the prediction's data.  Gradient for `sr` only."""
+    sr, hr = _ssim_args(sr, hr)
+    if double_backward():
+        return _ssim_composed(sr, hr, False)
+    return _SsimLoss.apply(sr, hr, _hip.SSIM_RANGE_BATCH).reshape(())
+
+
+def ssim_loss_per_sample(sr, hr):
+    """[N,C,H,W] x [N,C,H,W] -> [N]: the same term for every sample on its own (tasks adapted in lockstep), one launch."""
+    sr, hr = _ssim_args(sr, hr)
+    if double_backward():
+        return _ssim_composed(sr, hr, True)
+    return _SsimLoss.apply(sr, hr, _hip.SSIM_RANGE_PER_ROW)
+
+
+# --------------------------------------------------------------------------------------------
 # conv + bias + (leaky) ReLU with fused epilogues   (sepconv/model.py:172-194, model_utils.py:957-990)
 # --------------------------------------------------------------------------------------------
 # 3x3 / stride 1 convolutions run on savfi_conv3x3_f32 (Winograd on the fp32 matrix cores, bias + activation in its

@@ -1,15 +1,16 @@
-"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE}.
+"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM}.
 
 Surface follows the reference's ``Loss`` (loss.py:278-350): ``criterion(sr, hr) -> {TYPE: w*loss, ...,
-'total': sum}``.  L1 / MSE run on the fused savfi reduction kernel (one launch, no temporaries);
-the reference's VGG / GAN / SSIM / SuperSloMo terms are outside this path and are rejected loudly.
+'total': sum}``.  L1 / MSE run on the fused savfi reduction kernel (one launch, no temporaries), SSIM on the fused
+window kernel of csrc/ssim.hip (forward and gradient, the reference's data-dependent dynamic range decided on the device);
+the reference's VGG / GAN / SuperSloMo terms are outside this path and are rejected loudly.
 """
 import torch.nn as nn
 
 from . import hip_ops
 
-_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss}
-_KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample}
+_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss}
+_KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample, 'SSIM': hip_ops.ssim_loss_per_sample}
 
 
 class Loss(nn.modules.loss._Loss):
