@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define SAVFI_ABI_VERSION 21
+#define SAVFI_ABI_VERSION 22
 
 #define SAVFI_OK            0
 #define SAVFI_E_NULL       (-1)  /* a required pointer is NULL                          */
@@ -152,6 +152,27 @@ int savfi_sepconv_ws_errors_reset(void);
 /* Test hook: the spin limit of the kernels' bounded waits (default 1 << 19 spins of s_sleep 2).  A NEGATIVE limit makes every wait that does
  * not find its flag at once give up -- tests/ provoke the error path with it.  *previous (may be NULL) receives the old limit; launches issued afterwards use the new one. */
 int savfi_sepconv_ws_debug_spin_limit(int limit, int* previous);
+
+/* The work partition of the persistent SepConv kernels (K = 51, C = 3).  They launch at most one workgroup per CU; the phases of all
+ * strips in strip-major order (position g: strip g / nph, phase g % nph; strip s: sample s / ncol, strip s % ncol of the sample) are cut
+ * into one piece per workgroup, and a piece that crosses into the next strip starts a new run (a new LDS window) there.
+ *   kind SAVFI_SEPCONV_PARTITION_WS    the wave-specialised kernels (csrc/sepconv_ws.hip: Wo % 4 == 0, the strided / frames8 / pair entry
+ *                                      points; a pair launch over B samples is B' = 2 B here): phases of 4 rows, strips of 32 columns
+ *        SAVFI_SEPCONV_PARTITION_X6    one program per wave (csrc/sepconv_x6.hip: other widths): phases of 4 rows, strips of 32 columns
+ *        SAVFI_SEPCONV_PARTITION_FP32  the fp32 kernel of savfi_sepconv_bwd_f32 with one of gV / gH NULL: phases of 2 rows, strips of 64
+ * savfi_sepconv_partition answers with the host code the launches use and the functions the kernels evaluate: [*g0, *g1) is the piece of
+ * workgroup `block` in a launch planned for `cus` CUs (cus <= 0: the count launches plan for now).  Returns the grid size (<= cus), or
+ * SAVFI_E_NULL / SAVFI_E_SHAPE (a dimension <= 0, block outside the grid) / SAVFI_E_TOOBIG (the persistent kernels do not take the
+ * problem) / SAVFI_E_UNSUPPORTED (kind).  Needs no device. */
+#define SAVFI_SEPCONV_PARTITION_WS   0
+#define SAVFI_SEPCONV_PARTITION_X6   1
+#define SAVFI_SEPCONV_PARTITION_FP32 2
+int savfi_sepconv_partition(int kind, int B, int Ho, int Wo, int cus, int block, int* g0, int* g1);
+/* Test hook: the CU count that the launches of those kernels plan for.  0 restores the device's count; other values are clamped to
+ * [1, device count].  Host side only -- fewer workgroups that take more phases each is an ordinary launch (there is no dependency
+ * between workgroups) -- so tests/ can drive every state of the partition on any device.  *previous (may be NULL) receives the old
+ * setting (0 = the device's count); launches issued afterwards use the new one. */
+int savfi_sepconv_debug_cus(int cus, int* previous);
 
 /* ------------------------------------------------------------------------------------
  * VoxelFlow warp + blend (syn_type 'inter').

@@ -17,7 +17,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "savfi_hip.h")
 RULE_SGD, RULE_ADAM, RULE_ADAMAX_LSLR, RULE_ADAMAX_MSGD = 0, 1, 2, 3
 LR_SCALAR, LR_ELEMENT = 0, 1
 SSIM_RANGE_PER_ROW, SSIM_RANGE_BATCH, SSIM_RANGE_FIXED = 0, 1, 2
-ABI_VERSION = 21
+SEPCONV_PARTITION_WS, SEPCONV_PARTITION_X6, SEPCONV_PARTITION_FP32 = 0, 1, 2
+ABI_VERSION = 22
 
 _ERRORS = {-1: "SAVFI_E_NULL (a required pointer is NULL)",
            -2: "SAVFI_E_SHAPE (bad or inconsistent dimension)",
@@ -51,6 +52,8 @@ _PROTOTYPES = {
     "savfi_sepconv_ws_errors_peek": [],
     "savfi_sepconv_ws_errors_reset": [],
     "savfi_sepconv_ws_debug_spin_limit": [c_int, POINTER(c_int)],
+    "savfi_sepconv_partition": [c_int] * 6 + [POINTER(c_int), POINTER(c_int)],
+    "savfi_sepconv_debug_cus": [c_int, POINTER(c_int)],
     "savfi_conv3x3_dgrad_masked_f32": [_P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_convk_dgrad_masked_f32": [_P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_voxelwarp_fwd_f32": [_P, _P, _P, c_int, c_int, c_int, _P],

@@ -64,3 +64,8 @@ int savfi_sepconv_bwd_ws_launch(const float* in, const float* v, const float* h,
 int savfi_sepconv_fwd_ws_launch(const float* in, const float* v, const float* h, float* out, int B, int Ho, int Wo, int cus, int TB,
                                 const unsigned* cls, int taps_unit16, hipStream_t st, const float* in2 = nullptr,
                                 const unsigned* cls2 = nullptr);
+// The work partition of the persistent kernels above, answered by the host code their launches use: the piece [*g0, *g1) of the
+// strip-major phase list that workgroup `block` takes in a launch planned for `cus` CUs; returns the grid.  Reached through
+// savfi_sepconv_partition (csrc/sepconv.hip).
+int savfi_sepconv_ws_partition(int B, int Ho, int Wo, int cus, int block, int* g0, int* g1);
+int savfi_sepconv_x6_partition(int B, int Ho, int Wo, int cus, int block, int* g0, int* g1);

@@ -573,6 +573,12 @@ __global__ __launch_bounds__(MNT) void sepconv_bwd_mfma(const float* __restrict_
 // phase (two barriers), the full 64 only when a workgroup enters a strip.  Compute per phase is that of sepconv_bwd_mfma.
 // ------------------------------------------------------------------------------------------
 constexpr int PWIN = 64;                       // window rows per channel (power of two >= K + 1)
+// the piece [g0, g1) of the strip-major phase list (phases of 2 rows, strips of MC columns) that workgroup `block` of the persistent
+// kernel takes: per_wg consecutive phases.  The kernel and savfi_sepconv_partition() evaluate the same function.
+__host__ __device__ __forceinline__ void persistent_work_range(int total, int per_wg, int block, int& g0, int& g1) {
+  g0 = block * per_wg;
+  g1 = g0 + per_wg < total ? g0 + per_wg : total;
+}
 constexpr int PAHEAD = PWIN - (KFAST + 1);     // rows staged per refill (12)
 
 // rows [r_lo, r_lo + nrows) of the strip (b, x0) -> their circular slots, all three channels; thread -> (column, row group).
@@ -639,7 +645,8 @@ __global__ __launch_bounds__(MNT) void sepconv_bwd_mfma_p(const float* __restric
   const int wc = w & 3, wr = w >> 2;
   const int j = lane & 15, ks = lane >> 4;
   const int total = B * ncol * nph;
-  const int g0 = blockIdx.x * per_wg, g1 = min(g0 + per_wg, total);
+  int g0, g1;
+  persistent_work_range(total, per_wg, (int)blockIdx.x, g0, g1);
   if (g0 >= g1) return;
   const int Hi = Ho + K - 1, Wi = Wo + K - 1;
   const size_t plane = (size_t)Ho * Wo;
@@ -1081,7 +1088,9 @@ constexpr size_t persistent_lds_bytes() {
   return ((size_t)3 * PWIN * MLW + (size_t)(MNT / 64) * (KFAST + MKP) * 16) * sizeof(float);
 }
 
-int device_cu_count() {
+int debug_cus = 0;                             // savfi_sepconv_debug_cus: > 0 = the CU count the persistent launches plan for
+
+int device_cu_count_real() {
   static int cus[32] = {0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 256;
@@ -1091,6 +1100,11 @@ int device_cu_count() {
     n = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
   }
   return n;
+}
+// what the wave-specialised, the one-program-per-wave and the fp32 persistent launchers size their grids by
+int device_cu_count() {
+  const int n = device_cu_count_real();
+  return debug_cus > 0 ? (debug_cus < n ? debug_cus : n) : n;
 }
 
 // whole-tensor buffer resources: every tensor must stay below 2^31 bytes
@@ -1106,6 +1120,15 @@ bool persistent_ok(int B, int Ho, int Wo) {
   return taps < ((int64_t)1 << 31) && win < ((int64_t)1 << 31);
 }
 
+// the launch geometry of the fp32 persistent kernel: phases per strip, strips per sample, phases per workgroup and the grid
+int persistent_plan(int B, int Ho, int Wo, int cus, int& nph, int& ncol, int& per_wg) {
+  nph = savfi_cdiv(Ho, 2);
+  ncol = savfi_cdiv(Wo, MC);
+  const int64_t total = (int64_t)B * ncol * nph;
+  per_wg = savfi_cdiv(total, cus);
+  return savfi_cdiv(total, per_wg);
+}
+
 template <bool WV, bool WH>
 int launch_bwd_persistent_one(const float* in, const float* v, const float* h, const float* gO, float* gV, float* gH, int B,
                               int Ho, int Wo, hipStream_t st) {
@@ -1113,10 +1136,8 @@ int launch_bwd_persistent_one(const float* in, const float* v, const float* h, c
   static_assert(lds <= 160 * 1024, "LDS per CU");
   static uint32_t done = 0;
   if (int e = savfi_ensure_dynamic_lds((const void*)sepconv_bwd_mfma_p<KFAST, WV, WH>, lds, done)) return e;
-  const int nph = savfi_cdiv(Ho, 2), ncol = savfi_cdiv(Wo, MC);
-  const int64_t total = (int64_t)B * ncol * nph;
-  const int per_wg = savfi_cdiv(total, device_cu_count());
-  const int grid = savfi_cdiv(total, per_wg);
+  int nph, ncol, per_wg;
+  const int grid = persistent_plan(B, Ho, Wo, device_cu_count(), nph, ncol, per_wg);
   hipLaunchKernelGGL((sepconv_bwd_mfma_p<KFAST, WV, WH>), dim3(grid), dim3(MNT), lds, st, in, v, h, gO, gV, gH, B, Ho, Wo, nph, ncol,
                      per_wg);
   return savfi_launch_status();
@@ -1139,6 +1160,38 @@ int check_dims(int B, int C, int Ho, int Wo, int K) {
 }
 
 }  // namespace
+
+// Test hook: the CU count the persistent launches plan for (host side only: fewer workgroups that take more phases each is an ordinary
+// launch, there is no dependency between workgroups).  0 restores the device's count, anything else is clamped to [1, device count].
+// The previous setting (0 = the device's count) goes to *previous (may be NULL).
+extern "C" int savfi_sepconv_debug_cus(int cus, int* previous) {
+  if (previous) *previous = debug_cus;
+  debug_cus = cus == 0 ? 0 : (cus < 1 ? 1 : cus);
+  return SAVFI_OK;
+}
+
+// The piece [*g0, *g1) of the strip-major phase list that workgroup `block` of a persistent launch takes, from the host code the launches
+// size their grids with and the functions the kernels cut their pieces with.  Returns the grid, or a negative error.
+extern "C" int savfi_sepconv_partition(int kind, int B, int Ho, int Wo, int cus, int block, int* g0, int* g1) {
+  if (!g0 || !g1) return SAVFI_E_NULL;
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || block < 0) return SAVFI_E_SHAPE;
+  if (!persistent_ok(B, Ho, Wo)) return SAVFI_E_TOOBIG;
+  if (cus <= 0) cus = device_cu_count();
+  int grid;
+  switch (kind) {
+    case SAVFI_SEPCONV_PARTITION_WS: grid = savfi_sepconv_ws_partition(B, Ho, Wo, cus, block, g0, g1); break;
+    case SAVFI_SEPCONV_PARTITION_X6: grid = savfi_sepconv_x6_partition(B, Ho, Wo, cus, block, g0, g1); break;
+    case SAVFI_SEPCONV_PARTITION_FP32: {
+      int nph, ncol, per_wg;
+      grid = persistent_plan(B, Ho, Wo, cus, nph, ncol, per_wg);
+      persistent_work_range(B * ncol * nph, per_wg, block, *g0, *g1);
+      break;
+    }
+    default: return SAVFI_E_UNSUPPORTED;
+  }
+  if (block >= grid) return SAVFI_E_SHAPE;
+  return grid;
+}
 
 extern "C" int savfi_sepconv_fwd_f32(const float* in, const float* v, const float* h, float* out, int B,
                                      int C, int Ho, int Wo, int K, void* stream) {

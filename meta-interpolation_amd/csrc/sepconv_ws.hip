@@ -250,26 +250,6 @@ __device__ __forceinline__ int ws_lane() {
 // decided ON THE DEVICE, per call: savfi_frames8_classify_f32 leaves one word per classifier workgroup (non-zero = it met an element that is
 // not the fp32 quotient k / 255 to within 2 ulp), the <U8 = true> and <U8 = false> instances of a kernel are both launched and the one the
 // words do not select returns at once -- no host round trip (graph-capture safe), any other input takes the six-product path unchanged.
-// Which phases a workgroup takes.  The phases of all strips in strip-major order (position g: strip g / nph, phase g % nph) are cut into
-// gridDim.x consecutive pieces; a piece that crosses into the next strip starts a second RUN there (a new window: 64 rows through two
-// round trips, the first units' fetches, the pipeline's ramp -- 20 000 cycles = 1.5 phases measured, profiles/r05_ws_workgroup_times.txt:
-// workgroups with two runs 422 000 cycles, with one 402 000, and the launch waits for the slowest).  So the cut is made on a COST axis of
-// half phases on which every strip is WS_RUN_COST slots longer than its phases: a piece with a strip start inside gets that many half
-// phases fewer.  (An "aligned" order -- the workgroups of a chunk walking the same rows of neighbouring strips together -- was measured
-// slower three times, planar and unit-major taps alike: spread over the DRAM channels beats locality here; tools/r5/membench.hip.)
-#ifndef WS_RUN_COST
-#define WS_RUN_COST 2
-#endif
-__device__ __forceinline__ int ws_cost_to_phase(long long t, int nph) {
-  const int C = 2 * nph + WS_RUN_COST;
-  const int strip = (int)(t / C), r = (int)(t - (long long)strip * C);
-  return strip * nph + min(max((r - WS_RUN_COST + 1) >> 1, 0), nph);
-}
-__device__ __forceinline__ void ws_work_range(int S, int nph, int& g0, int& g1) {
-  const long long T = (long long)S * (2 * nph + WS_RUN_COST), G = gridDim.x, bx = blockIdx.x;
-  g0 = ws_cost_to_phase(bx * T / G, nph);
-  g1 = ws_cost_to_phase((bx + 1) * T / G, nph);
-}
 constexpr int CLS_WG = 256, CLS_NT = 1024;         // classifier grid: one 16-byte load of the words per lane of the consumer
 template <bool U8>
 __device__ __forceinline__ bool ws_frames8_mine(const unsigned* __restrict__ cls, const unsigned* __restrict__ cls2 = nullptr) {
@@ -331,11 +311,11 @@ __global__ __launch_bounds__(WNT) void sepconv_bwd_ws(const float* __restrict__ 
   unsigned* const fl = reinterpret_cast<unsigned*>(smem + WFLAG_OFF);
 
   [[maybe_unused]] const unsigned long long t_kernel0 = WS_TRACE ? __builtin_readcyclecounter() : 0ull;
-  // a workgroup's phases: positions [g0, g1) of the strip-major order (ws_work_range)
+  // a workgroup's phases: positions [g0, g1) of the strip-major order (ws_work_range, csrc/sepconv_x6_shared.h)
   int g0, g1;
   constexpr int base = 0;
   const int span = nph;
-  ws_work_range(B * ncol, nph, g0, g1);
+  ws_work_range(B * ncol, nph, (int)gridDim.x, (int)blockIdx.x, g0, g1);
   if (g0 >= g1) return;
   if (!ws_frames8_mine<U8>(cls, pair ? cls2 : nullptr)) return;
   const int Hi = Ho + XK - 1, Wi = Wo + XK - 1;
@@ -1105,11 +1085,11 @@ __global__ __launch_bounds__(WNT) void sepconv_fwd_ws(const float* __restrict__ 
   unsigned* const fl = reinterpret_cast<unsigned*>(smem + FFLAG_OFF);
 
   [[maybe_unused]] const unsigned long long t_kernel0 = WS_TRACE ? __builtin_readcyclecounter() : 0ull;
-  // a workgroup's phases: positions [g0, g1) of the strip-major order (ws_work_range)
+  // a workgroup's phases: positions [g0, g1) of the strip-major order (ws_work_range, csrc/sepconv_x6_shared.h)
   int g0, g1;
   constexpr int base = 0;
   const int span = nph;
-  ws_work_range(B * ncol, nph, g0, g1);
+  ws_work_range(B * ncol, nph, (int)gridDim.x, (int)blockIdx.x, g0, g1);
   if (g0 >= g1) return;
   if (!ws_frames8_mine<U8>(cls, pair ? cls2 : nullptr)) return;
   const int Hi = Ho + XK - 1, Wi = Wo + XK - 1;
@@ -1519,6 +1499,19 @@ unsigned* ws_watch_device_word() {
 }
 // one workgroup per CU (LDS), fewer when there are fewer phases than CUs
 static int ws_grid(int64_t total, int cus) { return (int)savfi_cdiv(total, savfi_cdiv(total, cus)); }
+// the launch geometry of both kernels: phases per strip, strips per sample and the grid
+static int ws_plan(int B, int Ho, int Wo, int cus, int& nph, int& ncol) {
+  nph = savfi_cdiv(Ho, XPR);
+  ncol = savfi_cdiv(Wo, XMC);
+  return ws_grid((int64_t)B * ncol * nph, cus);
+}
+// the piece [*g0, *g1) of workgroup `block` in a launch planned for `cus` CUs; returns the grid (declared in csrc/common.h)
+int savfi_sepconv_ws_partition(int B, int Ho, int Wo, int cus, int block, int* g0, int* g1) {
+  int nph, ncol;
+  const int grid = ws_plan(B, Ho, Wo, cus, nph, ncol);
+  ws_work_range(B * ncol, nph, grid, block, *g0, *g1);
+  return grid;
+}
 
 // cls: the words of savfi_frames8_classify_f32 on `in` (device memory; both instances of the kernel are launched and the device picks one),
 // or nullptr (the six-product kernel only)
@@ -1526,9 +1519,8 @@ int savfi_sepconv_bwd_ws_launch(const float* in, const float* v, const float* h,
                                 int Wo, int cus, int TB, const unsigned* cls, int taps_unit16, hipStream_t st, const float* in2,
                                 const unsigned* cls2) {
   const int pair = in2 != nullptr ? 1 : 0;          // B virtual samples = two frames per sample (see the kernel)
-  const int nph = savfi_cdiv(Ho, XPR), ncol = savfi_cdiv(Wo, XMC);
-  const int64_t total = (int64_t)B * ncol * nph;
-  const int grid = ws_grid(total, cus);
+  int nph, ncol;
+  const int grid = ws_plan(B, Ho, Wo, cus, nph, ncol);
   if (taps_unit16 && (Wo & 15) != 0) return SAVFI_E_UNSUPPORTED;
   static uint32_t done = 0, done8 = 0;
   if (cls) {
@@ -1550,9 +1542,8 @@ int savfi_sepconv_bwd_ws_launch(const float* in, const float* v, const float* h,
 int savfi_sepconv_fwd_ws_launch(const float* in, const float* v, const float* h, float* out, int B, int Ho, int Wo, int cus, int TB,
                                 const unsigned* cls, int taps_unit16, hipStream_t st, const float* in2, const unsigned* cls2) {
   const int pair = in2 != nullptr ? 1 : 0;
-  const int nph = savfi_cdiv(Ho, XPR), ncol = savfi_cdiv(Wo, XMC);
-  const int64_t total = (int64_t)B * ncol * nph;
-  const int grid = ws_grid(total, cus);
+  int nph, ncol;
+  const int grid = ws_plan(B, Ho, Wo, cus, nph, ncol);
   if (taps_unit16 && (Wo & 15) != 0) return SAVFI_E_UNSUPPORTED;
   static uint32_t done = 0, done8 = 0;
   if (cls) {

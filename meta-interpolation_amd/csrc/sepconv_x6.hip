@@ -50,7 +50,8 @@ __global__ __launch_bounds__(XNT) void sepconv_bwd_x6(const float* __restrict__ 
   float* const tailb = reinterpret_cast<float*>(smem + XTAIL_OFF + w * XTAILB);
 
   const int total = B * ncol * nph;
-  const int g0 = blockIdx.x * per_wg, g1 = min(g0 + per_wg, total);
+  int g0, g1;
+  x6_work_range(total, per_wg, (int)blockIdx.x, g0, g1);
   if (g0 >= g1) return;
   const int Hi = Ho + XK - 1, Wi = Wo + XK - 1;
   const unsigned plane_b = (unsigned)Ho * (unsigned)Wo * 4u;
@@ -468,7 +469,8 @@ __global__ __launch_bounds__(XNT) void sepconv_fwd_x6(const float* __restrict__ 
   float* const side = reinterpret_cast<float*>(smem + XSIDE_OFF);
 
   const int total = B * ncol * nph;
-  const int g0 = blockIdx.x * per_wg, g1 = min(g0 + per_wg, total);
+  int g0, g1;
+  x6_work_range(total, per_wg, (int)blockIdx.x, g0, g1);
   if (g0 >= g1) return;
   const int Hi = Ho + XK - 1, Wi = Wo + XK - 1;
   const unsigned plane_b = (unsigned)Ho * (unsigned)Wo * 4u;
@@ -700,13 +702,27 @@ __global__ __launch_bounds__(XNT) void sepconv_fwd_x6(const float* __restrict__ 
 
 }  // namespace
 
+// the launch geometry of both kernels: phases per strip, strips per sample, phases per workgroup and the grid
+static int x6_plan(int B, int Ho, int Wo, int cus, int& nph, int& ncol, int& per_wg) {
+  nph = savfi_cdiv(Ho, XPR);
+  ncol = savfi_cdiv(Wo, XMC);
+  const int64_t total = (int64_t)B * ncol * nph;
+  per_wg = savfi_cdiv(total, cus);
+  return savfi_cdiv(total, per_wg);
+}
+// the piece [*g0, *g1) of workgroup `block` in a launch planned for `cus` CUs; returns the grid (declared in csrc/common.h)
+int savfi_sepconv_x6_partition(int B, int Ho, int Wo, int cus, int block, int* g0, int* g1) {
+  int nph, ncol, per_wg;
+  const int grid = x6_plan(B, Ho, Wo, cus, nph, ncol, per_wg);
+  x6_work_range(B * ncol * nph, per_wg, block, *g0, *g1);
+  return grid;
+}
+
 // gV and gH of the K = 51, C = 3 op; every tensor below 2^31 bytes (the caller checks).  Declared in csrc/common.h.
 int savfi_sepconv_bwd_x6_launch(const float* in, const float* v, const float* h, const float* gO, float* gV, float* gH, int B, int Ho,
                                 int Wo, int cus, hipStream_t st) {
-  const int nph = savfi_cdiv(Ho, XPR), ncol = savfi_cdiv(Wo, XMC);
-  const int64_t total = (int64_t)B * ncol * nph;
-  const int per_wg = savfi_cdiv(total, cus);
-  const int grid = savfi_cdiv(total, per_wg);
+  int nph, ncol, per_wg;
+  const int grid = x6_plan(B, Ho, Wo, cus, nph, ncol, per_wg);
   if ((Wo & 3) == 0 && !X6_SCALAR_STORES) {
     static uint32_t done = 0;
     if (int e = savfi_ensure_dynamic_lds((const void*)sepconv_bwd_x6<true>, XLDS, done)) return e;
@@ -722,10 +738,8 @@ int savfi_sepconv_bwd_x6_launch(const float* in, const float* v, const float* h,
 // forward of the same op (declared in csrc/common.h)
 int savfi_sepconv_fwd_x6_launch(const float* in, const float* v, const float* h, float* out, int B, int Ho, int Wo, int cus,
                                 hipStream_t st) {
-  const int nph = savfi_cdiv(Ho, XPR), ncol = savfi_cdiv(Wo, XMC);
-  const int64_t total = (int64_t)B * ncol * nph;
-  const int per_wg = savfi_cdiv(total, cus);
-  const int grid = savfi_cdiv(total, per_wg);
+  int nph, ncol, per_wg;
+  const int grid = x6_plan(B, Ho, Wo, cus, nph, ncol, per_wg);
   if ((Wo & 3) == 0 && !X6_SCALAR_STORES) {
     static uint32_t done = 0;
     if (int e = savfi_ensure_dynamic_lds((const void*)sepconv_fwd_x6<true>, XLDS, done)) return e;

@@ -37,6 +37,39 @@ constexpr int XNREG = (XK + 3) / 4;              // gH leaves in 13 instructions
 constexpr int XNP = 7;                           // tap pairs per lane
 constexpr unsigned X_OOR = 0x80000000u;
 
+// Which phases a workgroup of the persistent kernels takes.  The phases of all strips in strip-major order (position g: strip g / nph,
+// phase g % nph; strip s: sample s / ncol, columns XMC (s % ncol) ..) are cut into one piece [g0, g1) per workgroup; a piece that crosses
+// into the next strip starts a new RUN there.  Host and device evaluate the SAME functions: the kernels with their gridDim.x / blockIdx.x,
+// savfi_sepconv_partition() (tests/test_sepconv_partition_cpu.py holds it to a transcription) with the numbers it is asked about.
+//
+// csrc/sepconv_x6.hip: per_wg = ceil(total / cus) consecutive phases each.
+__host__ __device__ __forceinline__ void x6_work_range(int total, int per_wg, int block, int& g0, int& g1) {
+  g0 = block * per_wg;
+  g1 = g0 + per_wg < total ? g0 + per_wg : total;
+}
+// csrc/sepconv_ws.hip: a second run costs a new window (64 rows through two round trips, the first units' fetches, the pipeline's ramp
+// -- 20 000 cycles = 1.5 phases measured, profiles/r05_ws_workgroup_times.txt: workgroups with two runs 422 000 cycles, with one 402 000,
+// and the launch waits for the slowest).  So the cut is made on a COST axis of half phases on which every strip is WS_RUN_COST slots longer
+// than its phases: a piece with a strip start inside gets that many half phases fewer.  (An "aligned" order -- the workgroups of a chunk
+// walking the same rows of neighbouring strips together -- was measured slower three times, planar and unit-major taps alike: spread
+// over the DRAM channels beats locality here; tools/r5/membench.hip.)
+#ifndef WS_RUN_COST
+#define WS_RUN_COST 2
+#endif
+__host__ __device__ __forceinline__ int ws_cost_to_phase(long long t, int nph) {
+  const int C = 2 * nph + WS_RUN_COST;
+  const int strip = (int)(t / C), r = (int)(t - (long long)strip * C);
+  int p = (r - WS_RUN_COST + 1) >> 1;
+  p = p < 0 ? 0 : p;
+  return strip * nph + (p < nph ? p : nph);
+}
+// S strips of nph phases, `grid` workgroups: the piece of workgroup `block`
+__host__ __device__ __forceinline__ void ws_work_range(int S, int nph, int grid, int block, int& g0, int& g1) {
+  const long long T = (long long)S * (2 * nph + WS_RUN_COST), G = grid, bx = block;
+  g0 = ws_cost_to_phase(bx * T / G, nph);
+  g1 = ws_cost_to_phase((bx + 1) * T / G, nph);
+}
+
 __device__ __forceinline__ float x6_bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
 #ifdef X6_EXP_LOADHIT      // experiment: every load hits the same few cache lines
   voff &= 0xfffu; soff = 0u;

@@ -1,0 +1,150 @@
+"""CPU: the work partition of the persistent SepConv kernels (csrc/sepconv_ws.hip, csrc/sepconv_x6.hip, sepconv_bwd_mfma_p of
+csrc/sepconv.hip) against its transcription in tests/sepconv_ref.py.
+
+tests/test_sepconv_partition_gpu.py claims to drive those kernels through every state of their partition -- several runs per workgroup,
+runs that start inside a strip, stretches across sample boundaries, long runs, ragged edges -- and computes the claims with the
+transcription.  Here the library's own answer (savfi_sepconv_partition: the host code the launches size their grids with, the
+__host__ __device__ functions the kernels cut their pieces with) is compared with it over a seeded sweep of (B, Ho, Wo, cus), so a change
+of WS_RUN_COST, XPR, XMC, MC or of a per_wg formula in C that the transcription does not follow fails here, on a machine without a GPU.
+The properties a partition must have whatever its formula are asserted on the library's pieces."""
+import ctypes
+import math
+import random
+
+import pytest
+import torch
+
+from meta_interpolation_amd import _hip
+from oracle import torch_ops as O
+from tests import sepconv_ref as R
+
+KINDS = {R.WS: "ws", R.X6: "x6", R.FP32: "fp32"}
+# the shapes of the product configurations and of the GPU cases (B, Ho, Wo, cus)
+FIXED = [(8, 256, 448, 256), (32, 256, 448, 256), (1, 720, 1280, 256), (64, 256, 448, 256), (4, 256, 448, 256), (1, 256, 448, 256),
+         (1, 384, 512, 256), (3, 130, 68, 1), (3, 130, 68, 5), (2, 67, 100, 3), (1, 258, 36, 1), (2, 256, 448, 16), (5, 6, 4, 2),
+         (1, 3, 4, 1), (1, 1, 1, 1), (1, 1, 1, 304), (2, 37, 45, 3), (1, 9, 70, 2), (1, 19, 41, 7), (1, 24, 40, 1), (7, 2, 4, 3)]
+HS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 15, 16, 17, 19, 24, 37, 63, 64, 65, 67, 128, 130, 131, 256, 258]
+WS_ = [1, 2, 3, 4, 5, 8, 12, 16, 28, 31, 32, 33, 36, 41, 45, 48, 63, 64, 65, 68, 70, 96, 100, 128, 129, 132, 448]
+BS = [1, 1, 2, 3, 4, 5, 8, 16]
+CUS = [1, 1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 31, 32, 33, 64, 100, 104, 128, 255, 256, 257, 304, 1000]
+
+
+def _sweep(count, seed):
+    rnd = random.Random(seed)
+    return FIXED + [(rnd.choice(BS), rnd.choice(HS), rnd.choice(WS_), rnd.choice(CUS)) for _ in range(count)]
+
+
+def _library_pieces(kind, B, Ho, Wo, cus):
+    lib = _hip.lib()
+    g0, g1 = ctypes.c_int(-1), ctypes.c_int(-1)
+    grid = lib.savfi_sepconv_partition(kind, B, Ho, Wo, cus, 0, ctypes.byref(g0), ctypes.byref(g1))
+    assert grid > 0, (kind, B, Ho, Wo, cus, grid)
+    out = [(g0.value, g1.value)]
+    for bx in range(1, grid):
+        assert lib.savfi_sepconv_partition(kind, B, Ho, Wo, cus, bx, ctypes.byref(g0), ctypes.byref(g1)) == grid
+        out.append((g0.value, g1.value))
+    assert lib.savfi_sepconv_partition(kind, B, Ho, Wo, cus, grid, ctypes.byref(g0), ctypes.byref(g1)) == -2      # no such workgroup
+    return out
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_partition_transcription_matches_the_library(seed):
+    seen = {k: dict(multi_run=0, mid_start=0, crossing=0, ragged_rows=0, ragged_strip=0, small_h=0, cus_above_total=0, one_cu=0)
+            for k in KINDS}
+    for B, Ho, Wo, cus in _sweep(700, seed):
+        for kind in KINDS:
+            if kind != R.FP32 and (Wo % 4 == 0) != (kind == R.WS):
+                continue                                  # the library routes widths that are a multiple of 4 to ws, the others to x6
+            case = (KINDS[kind], B, Ho, Wo, cus)
+            got = _library_pieces(kind, B, Ho, Wo, cus)
+            assert got == R.pieces(kind, B, Ho, Wo, cus), case
+            d = R.describe(kind, B, Ho, Wo, cus)
+            # what any partition has to deliver: ordered, disjoint pieces that tile [0, B ncol nph) exactly, on at most `cus` workgroups
+            R.check_tiling(got, d["total"])
+            assert len(got) <= cus and len(got) == d["grid"], case
+            if kind == R.WS:
+                # no piece holds more phases than its slots of the cost axis can (derivation: sepconv_ref.ws_piece_bound)
+                assert d["max_phases"] <= R.ws_piece_bound(B, Ho, Wo, d["grid"]), case
+                # ... which keeps every piece within WS_RUN_COST phases of the even share
+                assert d["max_phases"] <= R.cdiv(d["total"], d["grid"]) + R.WS_RUN_COST, case
+            else:
+                assert d["max_phases"] == R.cdiv(d["total"], cus) and d["empty"] == 0, case
+            s = seen[kind]
+            s["multi_run"] += d["max_runs"] > 2
+            s["mid_start"] += d["starts_mid_strip"] > 0
+            s["crossing"] += d["sample_crossings"] > 0
+            s["ragged_rows"] += d["ragged_rows"] != 0
+            s["ragged_strip"] += d["ragged_strip"] != 0
+            s["small_h"] += Ho < 4
+            s["cus_above_total"] += cus > d["total"]
+            s["one_cu"] += cus == 1
+    for kind, s in seen.items():                          # the sweep reaches every corner for every kernel family
+        assert all(s.values()), (KINDS[kind], s)
+
+
+def test_partition_examples():
+    """Hand-checked: the states the product shapes reach on 256 CUs, and what the GPU cases are there for."""
+    d = R.describe(R.WS, 8, 256, 448, 256)
+    assert (d["max_phases"], d["max_runs"], d["longest_run"]) == (29, 2, 29)
+    d = R.describe(R.WS, 32, 256, 448, 256)
+    assert (d["max_phases"], d["max_runs"], d["longest_run"]) == (113, 3, 64)
+    d = R.describe(R.WS, 1, 720, 1280, 256)
+    assert (d["max_phases"], d["max_runs"], d["longest_run"]) == (30, 2, 30)
+    d = R.describe(R.WS, 3, 130, 68, 1)                   # 3 samples x 3 strips of 33 phases on one workgroup
+    assert d["runs_per_wg"] == [9] and d["run_lengths"] == [33] and d["sample_crossings"] == 2
+    # the cost axis by hand: 2 strips of 3 phases, WS_RUN_COST = 2 -> 16 slots; 3 workgroups cut at slots 5 and 10: slot 5 is offset 5 of
+    # strip 0 = phase (5 - 1) >> 1 = 2, slot 10 is offset 2 of strip 1: still its phase 0
+    assert R.pieces(R.WS, 1, 12, 64, 3) == [(0, 2), (2, 3), (3, 6)]
+    assert _library_pieces(R.WS, 1, 12, 64, 3) == [(0, 2), (2, 3), (3, 6)]
+    # the other two kernels: per_wg = ceil(total / cus) consecutive phases; the fp32 kernel in phases of 2 rows on strips of 64 columns
+    assert R.pieces(R.X6, 1, 19, 41, 4) == [(0, 3), (3, 6), (6, 9), (9, 10)]
+    assert R.pieces(R.FP32, 1, 19, 41, 4) == [(0, 3), (3, 6), (6, 9), (9, 10)] and R.geometry(R.FP32, 1, 19, 141)[2:] == (10, 3, 30)
+
+
+def test_partition_refusals_and_the_cu_hook():
+    lib = _hip.lib()
+    g0, g1, prev = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(-7)
+    P = ctypes.byref
+    assert lib.savfi_sepconv_partition(R.WS, 1, 8, 8, 4, 0, None, P(g1)) == -1
+    assert lib.savfi_sepconv_partition(R.WS, 0, 8, 8, 4, 0, P(g0), P(g1)) == -2
+    assert lib.savfi_sepconv_partition(R.WS, 1, 8, 8, 4, -1, P(g0), P(g1)) == -2
+    assert lib.savfi_sepconv_partition(3, 1, 8, 8, 4, 0, P(g0), P(g1)) == -3
+    assert lib.savfi_sepconv_partition(R.WS, 64, 2048, 2048, 4, 0, P(g0), P(g1)) == -4       # beyond what the persistent kernels take
+    shapes = [(3, 130, 68), (2, 256, 448), (1, 9, 4)]
+
+    def planned(kind, B, Ho, Wo):                         # cus = 0: the count the launches plan for now
+        return lib.savfi_sepconv_partition(kind, B, Ho, Wo, 0, 0, P(g0), P(g1)), g0.value, g1.value
+
+    try:
+        assert lib.savfi_sepconv_debug_cus(0, P(prev)) == 0 and prev.value == 0              # nothing has set it: the device's count
+        own = [planned(k, *s) for k in KINDS for s in shapes]
+        assert lib.savfi_sepconv_debug_cus(5, P(prev)) == 0 and prev.value == 0
+        for k in KINDS:
+            for s in shapes:
+                want = R.pieces(k, *s, 5)
+                assert planned(k, *s) == (len(want),) + want[0], (k, s)
+        assert lib.savfi_sepconv_debug_cus(-3, P(prev)) == 0 and prev.value == 5             # clamped to 1
+        assert all(planned(k, *s)[0] == 1 for k in KINDS for s in shapes)
+        assert lib.savfi_sepconv_debug_cus(1 << 30, P(prev)) == 0 and prev.value == 1        # clamped to the device's count
+        assert [planned(k, *s) for k in KINDS for s in shapes] == own
+        assert lib.savfi_sepconv_debug_cus(0, P(prev)) == 0 and prev.value == 1 << 30
+        assert [planned(k, *s) for k in KINDS for s in shapes] == own
+    finally:
+        lib.savfi_sepconv_debug_cus(0, None)
+
+
+def test_float64_reference_agrees_with_autograd_through_the_oracle():
+    """tests/sepconv_ref.sepconv_f64 (tap loops, no autograd) against oracle.torch_ops.sepconv_torch and its autograd in double: two
+    evaluations that share no code agree to float64 rounding, at widths and heights around the chunking of both"""
+    for seed, (B, Ho, Wo) in enumerate([(2, 9, 13), (1, 3, 4), (1, 6, 33)]):
+        g = torch.Generator().manual_seed(seed)
+        inp = torch.randint(0, 256, (B, 3, Ho + R.K - 1, Wo + R.K - 1), generator=g).float().div(255)
+        v = torch.randn(B, R.K, Ho, Wo, generator=g) / math.sqrt(R.K)
+        h = torch.randn(B, R.K, Ho, Wo, generator=g) / math.sqrt(R.K)
+        gO = torch.randn(B, 3, Ho, Wo, generator=g)
+        out, gV, gH = R.sepconv_f64(inp, v, h, gO)
+        v64, h64 = v.double().requires_grad_(), h.double().requires_grad_()
+        ref = O.sepconv_torch(inp.double(), v64, h64)
+        ref.backward(gO.double())
+        for a, b in ((out, ref.detach()), (gV, v64.grad), (gH, h64.grad)):
+            assert (a - b).abs().max().item() <= 1e-13 * b.abs().max().item()
