@@ -3,6 +3,7 @@
 Every function here launches a hand-written gfx950 kernel through the C ABI (include/savfi_hip.h)
 on torch's current stream.  Device tensors only -- there is no CPU or eager-PyTorch fallback.
 """
+import collections
 import functools
 import ctypes
 import os
@@ -865,17 +866,15 @@ def convk_wgrad_preferred(K, Ci, Co, Ho, Wo, direct=False, N=None):
     return (Ci <= 32 and Ho * Wo >= 16384) or (Co >= 192 and Ho * Wo >= 4096)
 
 
-def _convk_geometry(weight, stride, padding, dilation, groups):
-    """(K, pad) if the layer is a square K x K / stride 1 / undilated / ungrouped convolution with symmetric padding the direct
-    kernels take, else None."""
-    one = lambda v, k: (v == k) if isinstance(v, int) else all(t == k for t in v)
-    K = int(weight.shape[-1])
-    if K not in (3, 5, 7) or int(weight.shape[-2]) != K or not one(stride, 1) or not one(dilation, 1) or groups != 1:
+def _conv_geometry(w_shape, stride, padding, dilation, groups=1):
+    """(K, pad) if the layer is a square K x K / stride 1 / undilated / ungrouped convolution with symmetric padding, else None.
+    (The one parser of a layer's geometry: which K and pad a kernel family takes is said where the route is chosen, conv_route.)"""
+    one = lambda v: v == 1 if isinstance(v, int) else all(t == 1 for t in v)
+    K = int(w_shape[-1])
+    if int(w_shape[-2]) != K or not one(stride) or not one(dilation) or groups != 1:
         return None
     pad = padding if isinstance(padding, int) else (padding[0] if padding[0] == padding[1] else -1)
-    if pad < 0 or pad > K - 1:
-        return None
-    return K, int(pad)
+    return (K, int(pad)) if pad >= 0 else None
 
 
 # Winograd F(4x4, 3x3) (csrc/winograd4.h; round 6): the 3x3 layers of at most 512 -> 512 channels, wherever its launch fills the chip --
@@ -904,17 +903,30 @@ def wino4_workgroups(N, Ci, Co, H, W, pad, mode=0):
     return max(n, 0)
 
 
-def convk_eligible(x, weight, stride, padding, dilation, groups=1, direct=False):
-    """Does this convolution (and its data gradient) run on the direct split-bf16 kernel?  weight [Co,Ci,K,K] or [T,Co,Ci,K,K]."""
-    if not (CONVK and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+def _layer(x_shape, w_shape, stride, padding, dilation, groups=1):
+    """(N, Ci, Co, H, W, K, pad) of a layer with a _conv_geometry on [N,C,H,W] maps, else None: what the threshold rules below take."""
+    geo = _conv_geometry(w_shape, stride, padding, dilation, groups)
+    if geo is None or len(x_shape) != 4:
+        return None
+    return (int(x_shape[0]), int(w_shape[-3]), int(w_shape[-4]), int(x_shape[2]), int(x_shape[3])) + geo
+
+
+def _form2(N, Ci, Co, H, W, pad):
+    """wino_form2 over integers."""
+    n = wino4_workgroups(int(N), int(Ci), int(Co), int(H), int(W), int(pad))
+    if n <= 0:
         return False
-    geo = _convk_geometry(weight, stride, padding, dilation, groups)
-    if geo is None:
+    # ... and on maps below ~400 pixels: a 12 x 16 map is 12 of a workgroup's 32 tiles, and the 36-point filter transform of a deep layer
+    # (2.25x F(2x2)'s: 151 MB per 512 -> 512 layer, direction and inner step at T = 4) costs more than the kernel saves there:
+    # 512 -> 512 @12x16, T = 4 x 2: 67 + 67 us + 92 us of transforms on F(4x4) against 53 + 52 + 41 on F(2x2)
+    return n < WINO4_MIN_WORKGROUPS or (H + 2 * pad - 2) * (W + 2 * pad - 2) < WINO4_MIN_PIXELS
+
+
+def _convk_admits(N, Ci, Co, H, W, K, pad, direct):
+    """Forward and data gradient of a layer on the direct split-bf16 kernel?  K in (3, 5, 7), 0 <= pad <= K - 1."""
+    if not CONVK or K not in (3, 5, 7) or pad > K - 1:
         return False
-    K, pad = geo
-    H, W = x.shape[2:]
     Ho, Wo = H + 2 * pad - K + 1, W + 2 * pad - K + 1
-    Co, Ci = weight.shape[-4], weight.shape[-3]
     if Ho < 1 or Wo < 1 or Ci * H * W >= (1 << 29) or Co * Ho * Wo >= (1 << 29):
         return False
     if K != 3 or direct:
@@ -922,7 +934,90 @@ def convk_eligible(x, weight, stride, padding, dilation, groups=1, direct=False)
     if not (Ho * Wo >= CONVK_3X3_MIN_PIXELS and (Ci <= 8 or (Ci >= 64 and Co >= 64 and Co % 64 == 0))):
         return False
     # (the <= 8-channel input layers stay here: an F(4x4) chunk is 8 reduction channels, half of them padding for 6 -> 32)
-    return Ci <= 8 or pad > 1 or not WINOGRAD_CONV or wino4_workgroups(int(x.shape[0]), int(Ci), int(Co), int(H), int(W), int(pad)) < WINO4_MIN_WORKGROUPS
+    return Ci <= 8 or pad > 1 or not WINOGRAD_CONV or wino4_workgroups(N, Ci, Co, H, W, pad) < WINO4_MIN_WORKGROUPS
+
+
+def _wino_admits(N, Ci, Co, H, W, K, pad, tasks, backward):
+    """A direction of a layer on the Winograd kernels by its tile count?  K == 3, pad in (0, 1).  Shared weights: WINO_MIN_TILES_* and
+    its batched variant; per-task weights: TASKS_MIN_TILES_*."""
+    if not WINOGRAD_CONV or K != 3 or pad not in (0, 1):
+        return False
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    if Ho < 1 or Wo < 1 or H * W < 4:
+        return False
+    tiles = N * ((Ho + 1) // 2) * ((Wo + 1) // 2)
+    if tasks:
+        return tiles >= (TASKS_MIN_TILES_BWD if backward else TASKS_MIN_TILES_FWD)
+    if N >= 2 and tiles >= (WINO_MIN_TILES_BWD_BATCHED if backward else WINO_MIN_TILES_FWD_BATCHED):
+        return True
+    return tiles >= (WINO_MIN_TILES_BWD if backward else WINO_MIN_TILES_FWD)
+
+
+def _wgrad3_admits(N, Ci, Co, H, W, K, pad, tasks):
+    """Weight gradient of a layer on savfi_conv3x3_wgrad*?  K == 3, pad in (0, 1); wherever its Winograd form runs (_wgrad_wino), else
+    shared weights: WGRAD_MIN_CI, WGRAD_MIN_PIXELS and the fill of the 64-pixel segments; per-task weights: TASKS_WGRAD_MIN_PIXELS."""
+    if not WINOGRAD_CONV or K != 3 or pad not in (0, 1):
+        return False
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    if Ho > 0 and Wo > 0 and _wgrad_wino(N, Ci, Co, Ho, Wo):
+        return True
+    if tasks:
+        return Ho * Wo >= TASKS_WGRAD_MIN_PIXELS
+    # the kernel works on 64-pixel row segments: a mostly empty last segment (CAIN's 160-wide maps: 83 % used) loses
+    fill = Wo / (64.0 * ((Wo + 63) // 64)) if Wo > 0 else 0.0
+    return Ci >= WGRAD_MIN_CI and Ho * Wo >= WGRAD_MIN_PIXELS and fill >= 0.85
+
+
+Route = collections.namedtuple("Route", "K pad fwd dgrad wgrad")
+_ATEN_ROUTE = Route(None, None, 'aten', 'aten', 'aten')
+
+
+def conv_route(x_shape, w_shape, stride, padding, dilation, groups=1, direct=False, reflect=False):
+    """Which kernels run a fused convolution of float32 maps on the device: the one place where that is decided, over integers (the knobs
+    of this module are read at every call).  w_shape [Co,Ci,K,K]: shared weights, [T,Co,Ci,K,K]: per-task weights.  Route:
+      fwd    'convk' (direct split-bf16), 'wino' (the Winograd form of the library's channel rule: F(4x4) up to 512 channels), 'wino2'
+             (F(2x2) although the channels say F(4x4): wino_form2), 'aten';
+      dgrad  the same on the filters transformed with the forward's, or 'conv3x3': the forward stayed on ATen but the backward thresholds
+             admit the Winograd kernel, which then transforms its own filter (conv3x3 / conv3x3_tasks);
+      wgrad  'convk' (csrc/convk_wgrad.hip), 'conv3x3' (savfi_conv3x3_wgrad*; Winograd or direct form: _wgrad_wino, in the launcher), 'aten';
+      K, pad of the square / stride 1 / undilated / ungrouped layer; None where it is not one (every direction on ATen)."""
+    layer = _layer(x_shape, w_shape, stride, padding, dilation, groups)
+    if layer is None:
+        return _ATEN_ROUTE
+    N, Ci, Co, H, W, K, pad = layer
+    tasks = len(w_shape) == 5
+    fwd = dgrad = wgrad = 'aten'
+    if _convk_admits(*layer, direct):
+        fwd = dgrad = 'convk'
+    else:
+        if _wino_admits(*layer, tasks, False):
+            fwd = 'wino2' if _form2(N, Ci, Co, H, W, pad) else 'wino'
+        if _wino_admits(*layer, tasks, True):
+            dgrad = fwd if fwd != 'aten' else 'conv3x3'
+    # 5x5 / 7x7 layers and plugins that asked for the direct form: weight gradient on the split-bf16 kernel as well; a mirrored border
+    # (shared weights, forward on the direct kernel: convk_reflect_eligible) exists there only
+    if reflect or (K in (3, 5, 7) and pad <= K - 1 and (fwd == 'convk' or K == 3)
+                   and convk_wgrad_preferred(K, Ci, Co, H + 2 * pad - K + 1, W + 2 * pad - K + 1, direct, N)):
+        wgrad = 'convk'
+    elif _wgrad3_admits(*layer, tasks):
+        wgrad = 'conv3x3'
+    return Route(K, pad, fwd, dgrad, wgrad)
+
+
+def _f32_map(x):
+    """The fused kernels take float32 [N,C,H,W] maps on the device: the precondition of every route but ATen's."""
+    return bool(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4)
+
+
+def _layer_of(x, weight, stride, padding, dilation, groups=1):
+    """_layer of tensors, for the predicates that ask one threshold rule of conv_route on its own; None also where x is no float32 map."""
+    return _layer(x.shape, weight.shape, stride, padding, dilation, groups) if _f32_map(x) else None
+
+
+def convk_eligible(x, weight, stride, padding, dilation, groups=1, direct=False):
+    """Does this convolution (and its data gradient) run on the direct split-bf16 kernel?  weight [Co,Ci,K,K] or [T,Co,Ci,K,K]."""
+    layer = _layer_of(x, weight, stride, padding, dilation, groups)
+    return layer is not None and _convk_admits(*layer, direct)
 
 
 def wino_form2(x, weight, pad):
@@ -930,15 +1025,7 @@ def wino_form2(x, weight, pad):
     launch would not fill the chip (small maps: the 64 x 64 fixtures, config C1): F(2x2) splits its reduction from 128 workgroups down and
     rounds 5x finer (an Adam-type inner rule turns F(4x4)'s rounding into flipped steps of the elements whose gradient is rounding
     noise: CAIN 64 x 64 + Adam).  The filters of such a layer are kind 'wino2' (savfi_conv3x3_*_form_f32 / bit 1 of `mode`)."""
-    Co, Ci = weight.shape[-4], weight.shape[-3]
-    H, W = int(x.shape[2]), int(x.shape[3])
-    n = wino4_workgroups(int(x.shape[0]), int(Ci), int(Co), H, W, int(pad))
-    if n <= 0:
-        return False
-    # ... and on maps below ~400 pixels: a 12 x 16 map is 12 of a workgroup's 32 tiles, and the 36-point filter transform of a deep layer
-    # (2.25x F(2x2)'s: 151 MB per 512 -> 512 layer, direction and inner step at T = 4) costs more than the kernel saves there:
-    # 512 -> 512 @12x16, T = 4 x 2: 67 + 67 us + 92 us of transforms on F(4x4) against 53 + 52 + 41 on F(2x2)
-    return n < WINO4_MIN_WORKGROUPS or (H + 2 * pad - 2) * (W + 2 * pad - 2) < WINO4_MIN_PIXELS
+    return _form2(x.shape[0], weight.shape[-3], weight.shape[-4], x.shape[2], x.shape[3], pad)
 
 
 # Packed / transformed filters of a module's OWN parameters are cached per weight version: a first-order meta-iteration
@@ -967,36 +1054,14 @@ def _filters(kind, weight, fwd, bwd, cache):
 
 
 def conv3x3_eligible(x, weight, stride, padding, dilation, groups, backward=False):
-    if not (WINOGRAD_CONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-        return False
-    one = lambda v, k: (v == k) if isinstance(v, int) else all(t == k for t in v)
-    pad = padding if isinstance(padding, int) else (padding[0] if padding[0] == padding[1] else -1)
-    if tuple(weight.shape[2:]) != (3, 3) or not one(stride, 1) or not one(dilation, 1) or groups != 1 or pad not in (0, 1):
-        return False
-    N, _, H, W = x.shape
-    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    if Ho < 1 or Wo < 1 or H * W < 4:
-        return False
-    tiles = N * ((Ho + 1) // 2) * ((Wo + 1) // 2)
-    if N >= 2 and tiles >= (WINO_MIN_TILES_BWD_BATCHED if backward else WINO_MIN_TILES_FWD_BATCHED):
-        return True
-    return tiles >= (WINO_MIN_TILES_BWD if backward else WINO_MIN_TILES_FWD)
+    """Do the Winograd thresholds admit this shared-weight layer (whatever the direct kernel says of it)?"""
+    layer = _layer_of(x, weight, stride, padding, dilation, groups)
+    return layer is not None and _wino_admits(*layer, False, backward)
 
 
 def conv3x3_wgrad_eligible(x, weight, stride, padding, dilation, groups):
-    if not (WINOGRAD_CONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-        return False
-    one = lambda v, k: (v == k) if isinstance(v, int) else all(t == k for t in v)
-    pad = padding if isinstance(padding, int) else (padding[0] if padding[0] == padding[1] else -1)
-    if tuple(weight.shape[2:]) != (3, 3) or not one(stride, 1) or not one(dilation, 1) or groups != 1 or pad not in (0, 1):
-        return False
-    _, Ci, H, W = x.shape
-    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    # the kernel works on 64-pixel row segments: a mostly empty last segment (CAIN's 160-wide maps: 83 % used) loses
-    fill = Wo / (64.0 * ((Wo + 63) // 64)) if Wo > 0 else 0.0
-    if Ho > 0 and Wo > 0 and _wgrad_wino(x.shape[0], Ci, weight.shape[0], Ho, Wo):
-        return True
-    return Ci >= WGRAD_MIN_CI and Ho * Wo >= WGRAD_MIN_PIXELS and fill >= 0.85
+    layer = _layer_of(x, weight, stride, padding, dilation, groups)
+    return layer is not None and _wgrad3_admits(*layer, False)
 
 
 # Weight gradients on a side stream.  In the backward of a first-order support pass the data-gradient chain (layer L's gx
@@ -1047,6 +1112,195 @@ def join_weight_gradients():
         torch.cuda.current_stream().wait_stream(side)
 
 
+def _aten_conv(x, w, stride, padding, dilation, groups, T):
+    """The layers no savfi kernel takes, on ATen (MIOpen), result [N,Co,Ho,Wo] contiguous.  Per-task weights (T not None, x contiguous):
+    ONE grouped convolution on small maps -- [n*T,C,H,W] viewed as [n,T*C,H,W] with groups = T --, one call per task on large ones."""
+    if T is None:
+        z = torch.nn.functional.conv2d(x, w, None, stride, padding, dilation, groups)
+        return z if z.is_contiguous() else z.contiguous()
+    N, Ci, H, W = x.shape
+    Co, n = w.shape[1], N // T
+    if _grouped_ok(x):
+        z = torch.nn.functional.conv2d(x.view(n, T * Ci, H, W), w.reshape(T * Co, Ci, *w.shape[3:]), None, stride, padding, dilation, T)
+        if not z.is_contiguous():
+            z = z.contiguous()
+    else:           # large map, no savfi kernel (5x5 / 7x7 / strided): one MIOpen call per task, results interleaved
+        xs = x.view(n, T, Ci, H, W)
+        z = torch.stack([torch.nn.functional.conv2d(xs[:, t], w[t], None, stride, padding, dilation) for t in range(T)], 1)
+    return z.view(N, Co, z.shape[-2], z.shape[-1])
+
+
+def _aten_conv_backward(gz, x, w, stride, padding, dilation, groups, T, need_x, need_w):
+    """(gx, gw) of _aten_conv (None where not asked for)."""
+    pair = lambda v: [v, v] if isinstance(v, int) else list(v)
+    conf = (None, pair(stride), pair(padding), pair(dilation), False, [0, 0])
+    if T is None:
+        gx, gw, _ = torch.ops.aten.convolution_backward(gz, x, w, *conf, groups, [need_x, need_w, False])
+        return (gx if need_x else None), (gw if need_w else None)
+    N, Ci, H, W = x.shape
+    Co, n = w.shape[1], N // T
+    Ho, Wo = gz.shape[2:]
+    if _grouped_ok(x):
+        gx, gw, _ = torch.ops.aten.convolution_backward(gz.view(n, T * Co, Ho, Wo), x.view(n, T * Ci, H, W), w.reshape(T * Co, Ci, *w.shape[3:]),
+                                                        *conf, T, [need_x, need_w, False])
+        return (gx.contiguous().view(N, Ci, H, W) if need_x else None), (gw.view(w.shape) if need_w else None)
+    gzs, xs = gz.view(n, T, Co, Ho, Wo), x.view(n, T, Ci, H, W)
+    per = [torch.ops.aten.convolution_backward(gzs[:, t].contiguous(), xs[:, t].contiguous(), w[t], *conf, 1, [need_x, need_w, False])
+           for t in range(T)]
+    return (torch.stack([p[0] for p in per], 1).view(N, Ci, H, W) if need_x else None), (torch.stack([p[1] for p in per], 0) if need_w else None)
+
+
+def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct, cache, reflect, in_slope, defer, out_unit16, T):
+    """The forward of both fused convolutions.  T = None: shared weights w [Co,Ci,K,K], b [Co] (_ConvBiasAct: `groups`, the module-owned
+    filter `cache`, the mirrored border `reflect`); else per-task weights w [T,Co,Ci,K,K], b [T,Co], sample s on task s % T
+    (_ConvBiasActTasks: `out_unit16`).  The route is decided here, once, and kept on ctx for the backward."""
+    # conv -> ReLU -> conv chains (model_utils.MetaSequential): `defer` -- the consumer of y applies THIS layer's activation
+    # derivative (the gradient arriving here is already d/dz); `in_slope` -- x is the activated output of a layer that deferred
+    # its derivative to this one: it is folded into this layer's data gradient (kernel epilogue where there is one)
+    if T is not None:
+        x = x.contiguous()          # (the grouped ATen call views it; the shared form leaves a strided x to ATen and the launchers)
+    route = conv_route(x.shape, w.shape, stride, padding, dilation, groups, direct, reflect) if _f32_map(x) else _ATEN_ROUTE
+    K, pad = route.K, route.pad
+    Co, Ci = w.shape[-4], w.shape[-3]
+    need_x = bool(ctx.needs_input_grad[0])
+    assert not reflect or route.fwd == 'convk', "mirrored borders: direct kernel only"
+    # out_unit16: the result's MEMORY is unit-major (its only consumer is FunctionSepconvPair(taps_unit16=True)); the cotangent that comes back
+    # is laid out like the shape says, so nothing changes in backward.  The caller has asked conv3x3_unit16_supported.
+    # out_unit16 == 2: the cotangent that comes back is unit-major as well (FunctionSepconvPair(..., grads_unit16=True)): only the
+    # data gradient may be asked for (the caller has checked conv3x3_in_unit16_supported and that w, b carry no gradient)
+    assert not out_unit16 or (slope == 1.0 and not defer and conv3x3_unit16_supported(x, w, pad)), \
+        "unit-major output: Winograd route (not the F(2x2) form of a small launch), no activation"
+    ctx.u_bwd = None
+    if route.fwd == 'convk':
+        u_fwd, ctx.u_bwd = _filters('convk', w, True, need_x, cache)
+        z = convk_tasks_pre(x, u_fwd, T or 1, Ci, Co, K, b, 0, slope, pad, direct, reflect)
+    elif route.fwd in ('wino', 'wino2'):
+        # both filter transforms of this layer in one launch: the data gradient of the same step will want the other one
+        u_fwd, ctx.u_bwd = _filters(route.fwd, w, True, need_x and route.dgrad == route.fwd, cache)
+        z = conv3x3_tasks_pre(x, u_fwd, T or 1, Ci, Co, b, 0, slope, pad, out_unit16=bool(out_unit16), f2=route.fwd == 'wino2')
+    else:
+        z = _aten_conv(x, w, stride, padding, dilation, groups, T)
+        if b is not None or slope != 1.0:
+            zb = b if b is not None else torch.zeros(w.shape[:-3], dtype=z.dtype, device=z.device)
+            _hip.require_cuda(z, zb)
+            rows, chans, hw = z.shape[0] // (T or 1), (T or 1) * Co, z.shape[2] * z.shape[3]      # [n*T,Co] maps = n rows of T*Co channels
+            lib = _hip.lib()
+            _hip.launch("bias_act_fwd", lambda: _hip.check(lib.savfi_bias_act_fwd_f32(
+                z.data_ptr(), zb.data_ptr(), rows, chans, hw, slope, _hip.current_stream()), "savfi_bias_act_fwd_f32"))
+    ctx.route, ctx.T, ctx.conf = route, T, (stride, padding, dilation, groups, slope)
+    ctx.in_slope, ctx.defer, ctx.reflect, ctx.gy_unit16 = in_slope, bool(defer), bool(reflect), int(out_unit16) == 2
+    ctx.direct, ctx.cache, ctx.w_version, ctx.has_bias = direct, cache, w._version, b is not None
+    ctx.wg_stream = weight_gradient_stream() if x.is_cuda else None
+    ctx.wg_uses = _weight_use_counter(w) if ctx.wg_stream is not None else None
+    ctx.save_for_backward(x, w, z)
+    if out_unit16:
+        tag_layout(z, UNIT16)           # the tensor's shape does not say how its memory is laid out: its consumer checks the tag
+    return z
+
+
+def _conv_backward(ctx, gy):
+    """(gx, gw, gb) of _conv_forward, on the route it kept: bias / activation backward, data gradient, weight gradient."""
+    x, w, y = ctx.saved_tensors
+    stride, padding, dilation, groups, slope = ctx.conf
+    route, T, direct = ctx.route, ctx.T, ctx.direct
+    K, pad = route.K, route.pad
+    Co, Ci = w.shape[-4], w.shape[-3]
+    N, _, Ho, Wo = y.shape
+    tasks = T or 1
+    need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+    # the filter packed / transformed at forward time is only valid for the weight version the forward saw
+    u_bwd = ctx.u_bwd if w._version == ctx.w_version else None
+    ctx.u_bwd = None
+    if T is not None:
+        # the cotangent's memory layout is a contract between two autograd functions that its shape cannot carry: the producer tags the
+        # tensor, and anything in between (a hook, an accumulation of two consumers' gradients, a clone) loses or contradicts the tag
+        require_layout(gy, UNIT16 if ctx.gy_unit16 else None, "the cotangent of conv_bias_act_tasks(out_unit16=%d)" % (2 if ctx.gy_unit16 else 1))
+    gy = gy.contiguous()
+    if ctx.gy_unit16:
+        assert not need_w and not need_b and slope == 1.0 and ctx.in_slope is None and route.fwd == 'wino', \
+            "a unit-major cotangent: data gradient of the Winograd route only"
+        if not need_x:
+            return None, None, None
+        if u_bwd is None:
+            u_bwd = _filters('wino', w, False, True, None)[1]
+        return conv3x3_dgrad_in_unit16(gy, u_bwd, T, Ci, Co, pad), None, None
+    identity = slope == 1.0 or ctx.defer     # no activation, or its derivative already applied by the consumer: gz is gy itself,
+    gz = gy if identity else torch.empty_like(gy)        # only the bias gradient is computed
+    mask, mslope = (x, ctx.in_slope) if (ctx.in_slope is not None and need_x) else (None, 1.0)
+    wgrad = route.wgrad if need_w else None
+    # a weight read by one op of the pass only: its gradient beside the data-gradient chain (decided here: the use count is final now)
+    side = ctx.wg_stream if (ctx.wg_stream is not None and ctx.wg_uses[0] == 1) else None
+    # the bias gradient rides on the weight gradient's read of gz where that is the all-taps direct kernel -- or, per-task weights only, the
+    # Winograd form -- and this function has nothing else to do with the cotangent (no activation, or its derivative left to the consumer):
+    # one pass over the map and two launches less per layer
+    # (not beside the Winograd weight gradient on the SIDE stream: a bias gradient autograd consumes on the compute stream -- stacked
+    # biases, a bias shared between ops -- must be produced there; the side-stream guard counts uses of the WEIGHT only)
+    fuse_b = bool(need_b and identity and (
+        (wgrad == 'convk' and convk_wgrad_tasks_sums_bias(x.shape, Co, tasks, K, pad, direct))
+        or (wgrad == 'conv3x3' and T is not None and side is None and conv3x3_wgrad_tasks_sums_bias(x.shape, Co, T, pad))))
+    gb = torch.empty(w.shape[:-3], dtype=gy.dtype, device=gy.device) if (need_b and not fuse_b) else None
+    if gb is not None or not identity:
+        rows, chans = N // tasks, tasks * Co                # [n*T,Co] maps = n rows of T*Co channels
+        lib = _hip.lib()
+        scratch = (torch.empty(_workspace_floats("savfi_bias_act_scratch_floats", rows, chans, Ho * Wo), dtype=gy.dtype, device=gy.device)
+                   if gb is not None else None)
+        _hip.launch("bias_act_bwd", lambda: _hip.check(lib.savfi_bias_act_bwd_f32(
+            gy.data_ptr(), (gy if identity else y).data_ptr(), None if identity else gz.data_ptr(),
+            None if gb is None else gb.data_ptr(), None if scratch is None else scratch.data_ptr(),
+            rows, chans, Ho * Wo, 1.0 if identity else slope, _hip.current_stream()), "savfi_bias_act_bwd_f32"))
+    gx = gw = None
+    if need_x and route.dgrad == 'convk':
+        if u_bwd is None:
+            u_bwd = _filters('convk', w, False, True, ctx.cache)[1]
+        if ctx.reflect:     # gradient of the mirrored (padded) extent = the full data gradient of the unpadded convolution, folded
+            gx = reflect_pad_bwd(convk_tasks_pre(gz, u_bwd, tasks, Ci, Co, K, None, 1, 1.0, 0, direct), pad)
+        else:
+            gx = convk_tasks_pre(gz, u_bwd, tasks, Ci, Co, K, None, 1, 1.0, pad, direct, mask=mask, mask_slope=mslope)
+            mask = None
+    elif need_x and route.dgrad in ('wino', 'wino2') and u_bwd is not None:
+        gx = conv3x3_tasks_pre(gz, u_bwd, tasks, Ci, Co, None, 1, 1.0, pad, mask=mask, mask_slope=mslope, f2=route.dgrad == 'wino2')
+        mask = None
+    elif need_x and route.dgrad != 'aten':
+        # the forward stayed on ATen ('conv3x3'), or the weight has changed since: the entry points that transform the filter themselves
+        # (shared weights: the form is the library's channel rule; per-task weights keep the forward's)
+        gx = conv3x3(gz, w, None, 1, 1.0, pad) if T is None else conv3x3_tasks(gz, w, None, 1, 1.0, pad, f2=route.dgrad == 'wino2')
+    if wgrad == 'convk':
+        gw = convk_wgrad_tasks(x, gz, tasks, K, pad, direct, ctx.reflect, want_bias=fuse_b)
+        if fuse_b:
+            gw, gb = gw
+        if T is None:
+            gw, gb = gw[0], (gb[0] if fuse_b else gb)
+    # the side stream: the shared form also runs the ATen weight gradient there, the per-task form the savfi one only
+    on_side = side is not None and (wgrad == 'conv3x3' or (wgrad == 'aten' and T is None))
+    if on_side:
+        # gz was produced on this stream just above: the side stream picks up from here
+        ready = torch.cuda.Event()
+        ready.record()
+        side.wait_event(ready)
+    if wgrad == 'conv3x3':
+        where = dict(stream=side.cuda_stream, extra_stream=side) if on_side else {}
+        if T is None:
+            gw = conv3x3_wgrad(x, gz, pad, **where)
+        else:
+            gw = conv3x3_wgrad_tasks(x, gz, T, pad, want_bias=fuse_b, **where)
+            if fuse_b:
+                gw, gb = gw
+    elif wgrad == 'aten' and on_side:
+        with torch.cuda.stream(side):
+            gw = _aten_conv_backward(gz, x, w, stride, padding, dilation, groups, None, False, True)[1]
+        gw.record_stream(torch.cuda.current_stream())      # consumed on this stream after the caller's join
+    if on_side:
+        x.record_stream(side)
+        gz.record_stream(side)
+    aten_x, aten_w = bool(need_x and route.dgrad == 'aten'), wgrad == 'aten' and not on_side
+    if aten_x or aten_w:
+        gx2, gw2 = _aten_conv_backward(gz, x, w, stride, padding, dilation, groups, T, aten_x, aten_w)
+        gx, gw = (gx2 if aten_x else gx), (gw2 if aten_w else gw)
+    if mask is not None and gx is not None:      # a route without the fused epilogue: the deferred derivative as its own pass
+        gx = mask_by_activation(gx, mask, mslope)
+    return gx, gw, gb
+
+
 class _ConvBiasAct(torch.autograd.Function):
     """y = act(conv2d(x, w) + b).  Large 3x3 convolutions run on the savfi Winograd/MFMA kernel with bias and
     activation in its epilogue; the others stay on MIOpen with the bias add and activation as ONE in-place kernel
@@ -1056,129 +1310,11 @@ class _ConvBiasAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct=False, cache=None, reflect=False, in_slope=None, defer=False):
-        # conv -> ReLU -> conv chains (model_utils.MetaSequential): `defer` -- the consumer of y applies THIS layer's activation
-        # derivative (the gradient arriving here is already d/dz); `in_slope` -- x is the activated output of a layer that deferred
-        # its derivative to this one: it is folded into this layer's data gradient (kernel epilogue where there is one)
-        pad = padding if isinstance(padding, int) else padding[0]
-        ctx.in_slope, ctx.defer = in_slope, bool(defer)
-        ctx.u_bwd, ctx.route, ctx.reflect = None, None, bool(reflect)
-        assert not reflect or convk_eligible(x, w, stride, padding, dilation, groups, direct), "mirrored borders: direct kernel only"
-        if convk_eligible(x, w, stride, padding, dilation, groups, direct):
-            K = int(w.shape[-1])
-            u_fwd, ctx.u_bwd = _filters('convk', w, True, bool(ctx.needs_input_grad[0]), cache)
-            z = convk_tasks_pre(x, u_fwd, 1, w.shape[1], w.shape[0], K, b, 0, slope, pad, direct, reflect)
-            ctx.route = 'convk'
-        elif conv3x3_eligible(x, w, stride, padding, dilation, groups):
-            want_bwd = ctx.needs_input_grad[0] and conv3x3_eligible(x, w, stride, padding, dilation, groups, backward=True)
-            ctx.route = 'wino2' if wino_form2(x, w, pad) else 'wino'
-            u_fwd, ctx.u_bwd = _filters(ctx.route, w, True, want_bwd, cache)
-            z = conv3x3_tasks_pre(x, u_fwd, 1, w.shape[1], w.shape[0], b, 0, slope, pad, f2=ctx.route == 'wino2')
-        else:
-            z = torch.nn.functional.conv2d(x, w, None, stride, padding, dilation, groups)
-            if not z.is_contiguous():
-                z = z.contiguous()
-            if b is not None or slope != 1.0:
-                zb = b if b is not None else torch.zeros(z.shape[1], dtype=z.dtype, device=z.device)
-                _hip.require_cuda(z, zb)
-                N, C, H, W = z.shape
-                lib = _hip.lib()
-                _hip.launch("bias_act_fwd", lambda: _hip.check(lib.savfi_bias_act_fwd_f32(
-                    z.data_ptr(), zb.data_ptr(), N, C, H * W, slope, _hip.current_stream()), "savfi_bias_act_fwd_f32"))
-        ctx.conf = (stride, padding, dilation, groups, slope)
-        ctx.direct, ctx.cache, ctx.w_version, ctx.has_bias = direct, cache, w._version, b is not None
-        ctx.wg_stream = weight_gradient_stream() if x.is_cuda else None
-        ctx.wg_uses = _weight_use_counter(w) if ctx.wg_stream is not None else None
-        ctx.save_for_backward(x, w, z)
-        return z
+        return _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct, cache, reflect, in_slope, defer, 0, None)
 
     @staticmethod
     def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        stride, padding, dilation, groups, slope = ctx.conf
-        gy = gy.contiguous()
-        N, C, H, W = y.shape
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
-        identity = slope == 1.0 or ctx.defer     # no activation, or its derivative already applied by the consumer: gz is gy itself,
-        gz = gy if identity else torch.empty_like(gy)        # only the bias gradient is computed
-        gb = torch.empty(C, dtype=gy.dtype, device=gy.device) if need_b else None
-        mask, mslope = (x, ctx.in_slope) if (ctx.in_slope is not None and need_x) else (None, 1.0)
-        pad = padding if isinstance(padding, int) else padding[0]
-        K = int(w.shape[-1])
-        # the bias gradient rides on the all-taps weight-gradient kernel's staging of the cotangent where this function has nothing else
-        # to do with it (no activation, or its derivative left to the consumer): one pass over the map and two launches less per layer
-        wgrad_is_convk = bool(need_w and (ctx.reflect or (_convk_geometry(w, stride, padding, dilation, groups) is not None
-                                                          and (ctx.route == 'convk' or K == 3)
-                                                          and convk_wgrad_preferred(K, w.shape[1], w.shape[0], H, W, ctx.direct, N))))
-        fuse_b = bool(need_b and identity and wgrad_is_convk and convk_wgrad_tasks_sums_bias(x.shape, C, 1, K, pad, ctx.direct))
-        if fuse_b:
-            gb = None
-        if (need_b and not fuse_b) or not identity:
-            lib = _hip.lib()
-            scratch = (torch.empty(_workspace_floats("savfi_bias_act_scratch_floats", N, C, H * W), dtype=gy.dtype, device=gy.device)
-                       if gb is not None else None)
-            _hip.launch("bias_act_bwd", lambda: _hip.check(lib.savfi_bias_act_bwd_f32(
-                gy.data_ptr(), (gy if identity else y).data_ptr(), None if identity else gz.data_ptr(),
-                None if gb is None else gb.data_ptr(), None if scratch is None else scratch.data_ptr(),
-                N, C, H * W, 1.0 if identity else slope, _hip.current_stream()), "savfi_bias_act_bwd_f32"))
-        gx = gw = None
-        # the filter packed / transformed at forward time is only valid for the weight version the forward saw
-        u_bwd = ctx.u_bwd if w._version == ctx.w_version else None
-        ctx.u_bwd = None
-        if need_x and ctx.route == 'convk':
-            if u_bwd is None:
-                u_bwd = _filters('convk', w, False, True, ctx.cache)[1]
-            if ctx.reflect:     # gradient of the mirrored (padded) extent = the full data gradient of the unpadded convolution, folded
-                gx = reflect_pad_bwd(convk_tasks_pre(gz, u_bwd, 1, w.shape[1], w.shape[0], K, None, 1, 1.0, 0, ctx.direct), pad)
-            else:
-                gx = convk_tasks_pre(gz, u_bwd, 1, w.shape[1], w.shape[0], K, None, 1, 1.0, pad, ctx.direct, mask=mask, mask_slope=mslope)
-                mask = None
-            need_x = False
-        if need_w and ctx.reflect:
-            res = convk_wgrad_tasks(x, gz, 1, K, pad, ctx.direct, True, want_bias=fuse_b)
-            gw, gb = (res[0][0], res[1][0]) if fuse_b else (res[0], gb)
-            need_w = False
-        elif need_x and conv3x3_eligible(x, w, stride, padding, dilation, groups, backward=True):
-            if u_bwd is not None and ctx.route in ('wino', 'wino2'):
-                gx = conv3x3_tasks_pre(gz, u_bwd, 1, w.shape[1], w.shape[0], None, 1, 1.0, pad, mask=mask, mask_slope=mslope,
-                                       f2=ctx.route == 'wino2')
-                mask = None
-            else:
-                gx = conv3x3(gz, w, None, 1, 1.0, pad)
-            need_x = False
-        pair = lambda v: [v, v] if isinstance(v, int) else list(v)
-        # 5x5 / 7x7 layers and plugins that asked for the direct form: weight gradient on the split-bf16 kernel as well
-        if need_w and _convk_geometry(w, stride, padding, dilation, groups) is not None and \
-                (ctx.route == 'convk' or K == 3) and convk_wgrad_preferred(K, w.shape[1], w.shape[0], gz.shape[2], gz.shape[3], ctx.direct, gz.shape[0]):
-            res = convk_wgrad_tasks(x, gz, 1, K, pad, ctx.direct, want_bias=fuse_b)
-            gw, gb = (res[0][0], res[1][0]) if fuse_b else (res[0], gb)
-            need_w = False
-        side = ctx.wg_stream if (ctx.wg_stream is not None and ctx.wg_uses[0] == 1) else None
-        if need_w and side is not None:
-            # gz was produced on this stream just above: the side stream picks up from here
-            ready = torch.cuda.Event()
-            ready.record()
-            side.wait_event(ready)
-            if conv3x3_wgrad_eligible(x, w, stride, padding, dilation, groups):
-                gw = conv3x3_wgrad(x, gz, pad, stream=side.cuda_stream, extra_stream=side)
-            else:
-                with torch.cuda.stream(side):
-                    _, gw, _ = torch.ops.aten.convolution_backward(gz, x, w, None, pair(stride), pair(padding), pair(dilation),
-                                                                   False, [0, 0], groups, [False, True, False])
-                gw.record_stream(torch.cuda.current_stream())      # consumed on this stream after the caller's join
-            x.record_stream(side)
-            gz.record_stream(side)
-            need_w = False
-        if need_w and conv3x3_wgrad_eligible(x, w, stride, padding, dilation, groups):
-            gw = conv3x3_wgrad(x, gz, pad)
-            need_w = False
-        if need_x or need_w:
-            gx2, gw2, _ = torch.ops.aten.convolution_backward(gz, x, w, None, pair(stride), pair(padding), pair(dilation),
-                                                              False, [0, 0], groups, [need_x, need_w, False])
-            gx = gx2 if need_x else gx
-            gw = gw2 if need_w else gw
-        if mask is not None and gx is not None:      # a route without the fused epilogue: the deferred derivative as its own pass
-            gx = mask_by_activation(gx, mask, mslope)
-        return gx, gw, gb, None, None, None, None, None, None, None, None, None, None
+        return _conv_backward(ctx, gy) + (None,) * 10
 
 
 # --------------------------------------------------------------------------------------------
@@ -1198,30 +1334,21 @@ TASKS_MIN_TILES_BWD = 1
 TASKS_WGRAD_MIN_PIXELS = 3000
 
 
-def _is3x3s1(weight, stride, padding, dilation):
-    one = lambda v, k: (v == k) if isinstance(v, int) else all(t == k for t in v)
-    pad = padding if isinstance(padding, int) else (padding[0] if padding[0] == padding[1] else -1)
-    return tuple(weight.shape[-2:]) == (3, 3) and one(stride, 1) and one(dilation, 1) and pad in (0, 1)
-
-
 def conv3x3_tasks_eligible(x, weight, stride, padding, dilation, backward=False):
-    if not (WINOGRAD_CONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _is3x3s1(weight, stride, padding, dilation)):
-        return False
-    pad = padding if isinstance(padding, int) else padding[0]
-    N, _, H, W = x.shape
-    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    if Ho < 1 or Wo < 1 or H * W < 4:
-        return False
-    return N * ((Ho + 1) // 2) * ((Wo + 1) // 2) >= (TASKS_MIN_TILES_BWD if backward else TASKS_MIN_TILES_FWD)
+    layer = _layer_of(x, weight, stride, padding, dilation)
+    return layer is not None and _wino_admits(*layer, True, backward)
 
 
 def conv3x3_wgrad_tasks_eligible(x, weight, stride, padding, dilation):
-    if not (WINOGRAD_CONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _is3x3s1(weight, stride, padding, dilation)):
-        return False
-    pad = padding if isinstance(padding, int) else padding[0]
-    N, Ci, H, W = x.shape
-    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    return Ho * Wo >= TASKS_WGRAD_MIN_PIXELS or (Ho > 0 and Wo > 0 and _wgrad_wino(N, Ci, weight.shape[1], Ho, Wo))
+    layer = _layer_of(x, weight, stride, padding, dilation)
+    return layer is not None and _wgrad3_admits(*layer, True)
+
+
+def _conv3x3_out(N, Ci, Co, H, W, pad, mode):
+    """(shape of the result, flops) of a savfi_conv3x3_* launch on an [N,*,H,W] map; mode 0: forward, 1: data gradient (of the cotangent)."""
+    grow = 2 * (pad if mode == 0 else 2 - pad) - 2
+    Ho, Wo = H + grow, W + grow
+    return (N, Co if mode == 0 else Ci, Ho, Wo), 18.0 * Ci * Co * N * (Ho * Wo if mode == 0 else H * W)
 
 
 def conv3x3_tasks(x, weight, bias=None, mode=0, slope=1.0, pad=1, f2=False):
@@ -1232,15 +1359,13 @@ def conv3x3_tasks(x, weight, bias=None, mode=0, slope=1.0, pad=1, f2=False):
     N, _, H, W = x.shape
     T, Co, Ci = weight.shape[:3]
     assert N % T == 0 and tuple(weight.shape[3:]) == (3, 3) and x.shape[1] == (Ci if mode == 0 else Co), (x.shape, weight.shape, mode)
-    I = Co if mode == 0 else Ci
-    grow = 2 * (pad if mode == 0 else 2 - pad) - 2
+    shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, mode)
     lib = _hip.lib()
     ws = torch.empty(_workspace_floats("savfi_conv3x3_tasks_workspace_floats", N, T, Ci, Co, H, W, int(pad), mode | fbit), dtype=x.dtype, device=x.device)
-    out = torch.empty((N, I, H + grow, W + grow), dtype=x.dtype, device=x.device)
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
     _hip.launch(_conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_tasks_f32(
         x.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), ws.data_ptr(),
-        N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), _hip.current_stream()), "savfi_conv3x3_tasks_f32"),
-        flops=18.0 * Ci * Co * out.shape[2] * out.shape[3] * N if mode == 0 else 18.0 * Ci * Co * H * W * N)
+        N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), _hip.current_stream()), "savfi_conv3x3_tasks_f32"), flops=flops)
     return out
 
 
@@ -1470,9 +1595,8 @@ def conv3x3_filters(weight, fwd=True, bwd=True, f2=False):
 def conv3x3_unit16_supported(x, w, pad):
     """Can the 3x3 layer (x [N,Ci,H,W], task weights w [T,Co,Ci,3,3], zero padding `pad`) write its result unit-major
     (savfi_conv3x3_tasks_pre_unit16_f32)?  It runs on the Winograd kernel, its width is a multiple of 16, no reduction split."""
-    if not (x.is_cuda and w.dim() == 5 and conv3x3_tasks_eligible(x, w, 1, pad, 1) and not convk_eligible(x, w, 1, pad, 1, 1, False)):
-        return False
-    if wino_form2(x, w, pad):          # a small launch runs the F(2x2) form (kind 'wino2'), whose unit-major entry points are the form-0 ones
+    # ('wino2' no: a small launch runs the F(2x2) form, whose unit-major entry points are the form-0 ones)
+    if not (_f32_map(x) and w.dim() == 5 and conv_route(x.shape, w.shape, 1, pad, 1).fwd == 'wino'):
         return False
     N, Ci, H, W = x.shape
     return int(_hip.lib().savfi_conv3x3_unit16_supported(N, w.shape[0], Ci, w.shape[1], H, W, int(pad))) == 1
@@ -1490,12 +1614,12 @@ def conv3x3_dgrad_in_unit16(gy, u, T, Ci, Co, pad):
     gy = gy.contiguous()
     _hip.require_cuda(gy, u)
     N, _, H, W = gy.shape
-    grow = 2 * (2 - pad) - 2
-    out = torch.empty((N, Ci, H + grow, W + grow), dtype=gy.dtype, device=gy.device)
+    shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 1)
+    out = torch.empty(shape, dtype=gy.dtype, device=gy.device)
     lib = _hip.lib()
     _hip.launch(_conv3x3_name(Ci, Co, "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_dgrad_in_unit16_f32(
         gy.data_ptr(), u.data_ptr(), out.data_ptr(), N, T, Ci, Co, H, W, int(pad), _hip.current_stream()),
-        "savfi_conv3x3_dgrad_in_unit16_f32"), flops=18.0 * Ci * Co * H * W * N)
+        "savfi_conv3x3_dgrad_in_unit16_f32"), flops=flops)
     return out
 
 
@@ -1513,38 +1637,36 @@ def conv3x3_tasks_pre(x, u, T, Ci, Co, bias=None, mode=0, slope=1.0, pad=1, mask
         return _conv3x3_dgrad_masked(x, u, T, Ci, Co, pad, mask.contiguous(), mask_slope, fbit)
     N, _, H, W = x.shape
     assert N % T == 0 and x.shape[1] == (Ci if mode == 0 else Co), (x.shape, T, Ci, Co, mode)
-    I = Co if mode == 0 else Ci
-    grow = 2 * (pad if mode == 0 else 2 - pad) - 2
+    shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, mode)
     lib = _hip.lib()
     if out_unit16:
         assert mode == 0 and not f2
-        out = torch.empty((N, I, H + grow, W + grow), dtype=x.dtype, device=x.device)
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
         _hip.launch(_conv3x3_name(Ci, Co, "fwd"), lambda: _hip.check(lib.savfi_conv3x3_tasks_pre_unit16_f32(
             x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), N, T, Ci, Co, H, W, int(pad), float(slope),
-            _hip.current_stream()), "savfi_conv3x3_tasks_pre_unit16_f32"), flops=18.0 * Ci * Co * out.shape[2] * out.shape[3] * N)
+            _hip.current_stream()), "savfi_conv3x3_tasks_pre_unit16_f32"), flops=flops)
         return out
     nws = _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, T, Ci, Co, H, W, int(pad), mode | fbit)
     ws = torch.empty(nws, dtype=x.dtype, device=x.device) if nws else None
-    out = torch.empty((N, I, H + grow, W + grow), dtype=x.dtype, device=x.device)
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
     name = ("conv3x3_" + ("fwd" if mode == 0 else "bwd_data")) if f2 else _conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data")
     _hip.launch(name, lambda: _hip.check(lib.savfi_conv3x3_tasks_pre_f32(
         x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), None if ws is None else ws.data_ptr(),
-        N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), _hip.current_stream()), "savfi_conv3x3_tasks_pre_f32"),
-        flops=18.0 * Ci * Co * out.shape[2] * out.shape[3] * N if mode == 0 else 18.0 * Ci * Co * H * W * N)
+        N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), _hip.current_stream()), "savfi_conv3x3_tasks_pre_f32"), flops=flops)
     return out
 
 
 def _conv3x3_dgrad_masked(gy, u, T, Ci, Co, pad, mask, mask_slope, fbit=0):
     N, _, H, W = gy.shape
-    grow = 2 * (2 - pad) - 2
-    out = torch.empty((N, Ci, H + grow, W + grow), dtype=gy.dtype, device=gy.device)
+    shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 1)
+    out = torch.empty(shape, dtype=gy.dtype, device=gy.device)
     assert mask.shape == out.shape, (mask.shape, out.shape)
     lib = _hip.lib()
     nws = _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, T, Ci, Co, H, W, int(pad), 1 | fbit)
     ws = torch.empty(nws, dtype=gy.dtype, device=gy.device) if nws else None
     _hip.launch("conv3x3_bwd_data" if fbit else _conv3x3_name(Ci, Co, "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_dgrad_masked_form_f32(
         gy.data_ptr(), u.data_ptr(), mask.data_ptr(), float(mask_slope), out.data_ptr(), None if ws is None else ws.data_ptr(),
-        N, T, Ci, Co, H, W, int(pad), fbit, _hip.current_stream()), "savfi_conv3x3_dgrad_masked_form_f32"), flops=18.0 * Ci * Co * H * W * N)
+        N, T, Ci, Co, H, W, int(pad), fbit, _hip.current_stream()), "savfi_conv3x3_dgrad_masked_form_f32"), flops=flops)
     return out
 
 
@@ -1843,168 +1965,11 @@ class _ConvBiasActTasks(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, stride, padding, dilation, slope, direct=False, in_slope=None, defer=False, out_unit16=False):
-        x = x.contiguous()
-        ctx.in_slope, ctx.defer = in_slope, bool(defer)          # see _ConvBiasAct.forward
-        # out_unit16 == 2: the cotangent that comes back is unit-major as well (FunctionSepconvPair(..., grads_unit16=True)): only the
-        # data gradient may be asked for (the caller has checked conv3x3_in_unit16_supported and that w, b carry no gradient)
-        ctx.gy_unit16 = int(out_unit16) == 2
-        out_unit16 = bool(out_unit16)
-        T, Co, Ci = w.shape[:3]
-        N, _, H, W = x.shape
-        n = N // T
-        pad = padding if isinstance(padding, int) else padding[0]
-        ctx.u_bwd, ctx.route = None, None
-        if out_unit16:
-            # the result's MEMORY is unit-major (its only consumer is FunctionSepconvPair(taps_unit16=True)); the cotangent that comes back
-            # is laid out like the shape says, so nothing changes in backward.  The caller has asked conv3x3_unit16_supported.
-            assert slope == 1.0 and not defer and conv3x3_unit16_supported(x, w, pad), "unit-major output: Winograd route, no activation"
-        if convk_eligible(x, w, stride, padding, dilation, 1, direct):
-            u_fwd, ctx.u_bwd = convk_filters(w, True, bool(ctx.needs_input_grad[0]))
-            z = convk_tasks_pre(x, u_fwd, T, Ci, Co, int(w.shape[-1]), b, 0, slope, pad, direct)
-            ctx.route = 'convk'
-        elif conv3x3_tasks_eligible(x, w, stride, padding, dilation):
-            # both filter transforms of this layer in one launch: the data gradient of the same step will want the other one
-            want_bwd = ctx.needs_input_grad[0] and conv3x3_tasks_eligible(x, w, stride, padding, dilation, backward=True)
-            f2 = wino_form2(x, w, pad)
-            assert not (f2 and out_unit16), "unit-major output: not on the F(2x2) form of a small launch (conv3x3_unit16_supported says so)"
-            u_fwd, ctx.u_bwd = conv3x3_filters(w, True, want_bwd, f2=f2)
-            z = conv3x3_tasks_pre(x, u_fwd, T, Ci, Co, b, 0, slope, pad, out_unit16=out_unit16, f2=f2)
-            ctx.route = 'wino2' if f2 else 'wino'
-        else:
-            if _grouped_ok(x):
-                z = torch.nn.functional.conv2d(x.view(n, T * Ci, H, W), w.reshape(T * Co, Ci, *w.shape[3:]), None, stride, padding,
-                                               dilation, T)
-                if not z.is_contiguous():
-                    z = z.contiguous()
-            else:           # large map, no savfi kernel (5x5 / 7x7 / strided): one MIOpen call per task, results interleaved
-                xs = x.view(n, T, Ci, H, W)
-                z = torch.stack([torch.nn.functional.conv2d(xs[:, t], w[t], None, stride, padding, dilation) for t in range(T)], 1)
-                z = z.view(N, Co, z.shape[3], z.shape[4])
-            if b is not None or slope != 1.0:
-                zb = b if b is not None else torch.zeros((T, Co), dtype=z.dtype, device=z.device)
-                _hip.require_cuda(z, zb)
-                lib = _hip.lib()
-                hw = z.shape[-2] * z.shape[-1]
-                _hip.launch("bias_act_fwd", lambda: _hip.check(lib.savfi_bias_act_fwd_f32(
-                    z.data_ptr(), zb.data_ptr(), n, T * Co, hw, slope, _hip.current_stream()), "savfi_bias_act_fwd_f32"))
-            z = z.view(N, Co, z.shape[-2], z.shape[-1])
-        ctx.conf = (stride, padding, dilation, slope)
-        ctx.has_bias, ctx.direct, ctx.w_version = b is not None, direct, w._version
-        ctx.wg_stream = weight_gradient_stream() if x.is_cuda else None
-        ctx.wg_uses = _weight_use_counter(w) if ctx.wg_stream is not None else None
-        ctx.save_for_backward(x, w, z)
-        if out_unit16:
-            tag_layout(z, UNIT16)           # the tensor's shape does not say how its memory is laid out: its consumer checks the tag
-        return z
+        return _conv_forward(ctx, x, w, b, stride, padding, dilation, 1, slope, direct, None, False, in_slope, defer, int(out_unit16), w.shape[0])
 
     @staticmethod
     def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        stride, padding, dilation, slope = ctx.conf
-        # the cotangent's memory layout is a contract between two autograd functions that its shape cannot carry: the producer tags the
-        # tensor, and anything in between (a hook, an accumulation of two consumers' gradients, a clone) loses or contradicts the tag
-        require_layout(gy, UNIT16 if ctx.gy_unit16 else None, "the cotangent of conv_bias_act_tasks(out_unit16=%d)" % (2 if ctx.gy_unit16 else 1))
-        gy = gy.contiguous()
-        T, Co, Ci = w.shape[:3]
-        N, _, Ho, Wo = y.shape
-        n = N // T
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if ctx.gy_unit16:
-            assert not need_w and not (need_b and ctx.has_bias) and slope == 1.0 and ctx.in_slope is None and ctx.route == 'wino', \
-                "a unit-major cotangent: data gradient of the Winograd route only"
-            if not need_x:
-                return (None,) * 11
-            pad = padding if isinstance(padding, int) else padding[0]
-            u_bwd = ctx.u_bwd if w._version == ctx.w_version else None
-            ctx.u_bwd = None
-            if u_bwd is None:
-                u_bwd = conv3x3_filters(w, False, True)[1]
-            return (conv3x3_dgrad_in_unit16(gy, u_bwd, T, Ci, Co, pad),) + (None,) * 10
-        identity = slope == 1.0 or ctx.defer
-        gz = gy if identity else torch.empty_like(gy)
-        need_b = need_b and ctx.has_bias
-        mask, mslope = (x, ctx.in_slope) if (ctx.in_slope is not None and need_x) else (None, 1.0)
-        # the bias gradient rides on the weight gradient's read of gz where that is the Winograd form or the all-taps direct kernel and this
-        # function has nothing else to do with the cotangent (no activation derivative to apply here): one pass over the map less
-        pad_ = padding if isinstance(padding, int) else padding[0]
-        K_ = int(w.shape[-1])
-        wgrad_is_convk = bool(need_w and _convk_geometry(w, stride, padding, dilation, 1) is not None and (ctx.route == 'convk' or K_ == 3)
-                              and convk_wgrad_preferred(K_, Ci, Co, Ho, Wo, ctx.direct, x.shape[0]))
-        wgrad_is_wino3 = need_w and not wgrad_is_convk and conv3x3_wgrad_tasks_eligible(x, w, stride, padding, dilation)
-        # (not beside the Winograd weight gradient on the SIDE stream: a bias gradient autograd consumes on the compute stream -- stacked
-        # biases, a bias shared between ops -- must be produced there; the side-stream guard counts uses of the WEIGHT only)
-        wino3_on_side = wgrad_is_wino3 and ctx.wg_stream is not None and ctx.wg_uses[0] == 1
-        fuse_b = bool(need_b and identity and ((wgrad_is_wino3 and not wino3_on_side and conv3x3_wgrad_tasks_sums_bias(x.shape, Co, T, pad_))
-                                               or (wgrad_is_convk and convk_wgrad_tasks_sums_bias(x.shape, Co, T, K_, pad_, ctx.direct))))
-        gb = torch.empty((T, Co), dtype=gy.dtype, device=gy.device) if (need_b and not fuse_b) else None
-        if (need_b and not fuse_b) or not identity:
-            lib = _hip.lib()
-            scratch = (torch.empty(_workspace_floats("savfi_bias_act_scratch_floats", n, T * Co, Ho * Wo), dtype=gy.dtype, device=gy.device)
-                       if gb is not None else None)
-            _hip.launch("bias_act_bwd", lambda: _hip.check(lib.savfi_bias_act_bwd_f32(
-                gy.data_ptr(), (gy if identity else y).data_ptr(), None if identity else gz.data_ptr(),
-                None if gb is None else gb.data_ptr(), None if scratch is None else scratch.data_ptr(),
-                n, T * Co, Ho * Wo, 1.0 if identity else slope, _hip.current_stream()), "savfi_bias_act_bwd_f32"))
-        gx = gw = None
-        pad = padding if isinstance(padding, int) else padding[0]
-        K = int(w.shape[-1])
-        u_bwd = ctx.u_bwd if w._version == ctx.w_version else None      # valid for the weight version the forward saw only
-        ctx.u_bwd = None
-        if need_x and ctx.route == 'convk':
-            if u_bwd is None:
-                u_bwd = convk_filters(w, False, True)[1]
-            gx = convk_tasks_pre(gz, u_bwd, T, Ci, Co, K, None, 1, 1.0, pad, ctx.direct, mask=mask, mask_slope=mslope)
-            mask = None
-            need_x = False
-        elif need_x and conv3x3_tasks_eligible(x, w, stride, padding, dilation, backward=True):
-            if u_bwd is not None and ctx.route in ('wino', 'wino2'):
-                gx = conv3x3_tasks_pre(gz, u_bwd, T, Ci, Co, None, 1, 1.0, pad, mask=mask, mask_slope=mslope, f2=ctx.route == 'wino2')
-                mask = None
-            else:
-                gx = conv3x3_tasks(gz, w, None, 1, 1.0, pad, f2=ctx.route == 'wino2')
-            need_x = False
-        if wgrad_is_convk:
-            gw = convk_wgrad_tasks(x, gz, T, K, pad, ctx.direct, want_bias=fuse_b)
-            if fuse_b:
-                gw, gb = gw
-            need_w = False
-        if need_w and conv3x3_wgrad_tasks_eligible(x, w, stride, padding, dilation):
-            side = ctx.wg_stream if (ctx.wg_stream is not None and ctx.wg_uses[0] == 1) else None
-            if side is not None:     # beside the data-gradient chain (see _ConvBiasAct.backward); joined by the caller
-                ready = torch.cuda.Event()
-                ready.record()
-                side.wait_event(ready)
-                gw = conv3x3_wgrad_tasks(x, gz, T, pad, stream=side.cuda_stream, extra_stream=side, want_bias=fuse_b)
-                x.record_stream(side)
-                gz.record_stream(side)
-            else:
-                gw = conv3x3_wgrad_tasks(x, gz, T, pad, want_bias=fuse_b)
-            if fuse_b:
-                gw, gb = gw
-            need_w = False
-        if need_x or need_w:
-            pair = lambda v: [v, v] if isinstance(v, int) else list(v)
-            H, W = x.shape[2:]
-            if _grouped_ok(x):
-                gx2, gw2, _ = torch.ops.aten.convolution_backward(
-                    gz.view(n, T * Co, Ho, Wo), x.view(n, T * Ci, H, W), w.reshape(T * Co, Ci, *w.shape[3:]), None, pair(stride),
-                    pair(padding), pair(dilation), False, [0, 0], T, [need_x, need_w, False])
-                if need_x:
-                    gx = gx2.contiguous().view(N, Ci, H, W)
-                if need_w:
-                    gw = gw2.view(w.shape)
-            else:
-                gzs, xs = gz.view(n, T, Co, Ho, Wo), x.view(n, T, Ci, H, W)
-                per = [torch.ops.aten.convolution_backward(gzs[:, t].contiguous(), xs[:, t].contiguous(), w[t], None, pair(stride),
-                                                           pair(padding), pair(dilation), False, [0, 0], 1, [need_x, need_w, False])
-                       for t in range(T)]
-                if need_x:
-                    gx = torch.stack([p[0] for p in per], 1).view(N, Ci, H, W)
-                if need_w:
-                    gw = torch.stack([p[1] for p in per], 0)
-        if mask is not None and gx is not None:
-            gx = mask_by_activation(gx, mask, mslope)
-        return gx, gw, gb, None, None, None, None, None, None, None, None
+        return _conv_backward(ctx, gy) + (None,) * 8
 
 
 def conv_bias_act_tasks(x, weight, bias, stride=1, padding=0, dilation=1, slope=0.0, direct=False, in_slope=None, defer=False,
@@ -2034,15 +1999,13 @@ def conv3x3(x, weight, bias=None, mode=0, slope=1.0, pad=1):
     N, _, H, W = x.shape
     Co, Ci = weight.shape[:2]
     assert tuple(weight.shape[2:]) == (3, 3) and x.shape[1] == (Ci if mode == 0 else Co), (x.shape, weight.shape, mode)
-    K, I = (Ci, Co) if mode == 0 else (Co, Ci)
-    grow = 2 * (pad if mode == 0 else 2 - pad) - 2
+    shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, mode)
     lib = _hip.lib()
     ws = torch.empty(_workspace_floats("savfi_conv3x3_workspace_floats", N, Ci, Co, H, W, int(pad), mode), dtype=x.dtype, device=x.device)
-    out = torch.empty((N, I, H + grow, W + grow), dtype=x.dtype, device=x.device)
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
     _hip.launch(_conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_f32(
         x.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), ws.data_ptr(),
-        N, Ci, Co, H, W, int(pad), mode, float(slope), _hip.current_stream()), "savfi_conv3x3_f32"),
-        flops=18.0 * Ci * Co * out.shape[2] * out.shape[3] * N if mode == 0 else 18.0 * Ci * Co * H * W * N)
+        N, Ci, Co, H, W, int(pad), mode, float(slope), _hip.current_stream()), "savfi_conv3x3_f32"), flops=flops)
     return out
 
 
