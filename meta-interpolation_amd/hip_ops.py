@@ -1028,31 +1028,6 @@ def wino_form2(x, weight, pad):
     return _form2(x.shape[0], weight.shape[-3], weight.shape[-4], x.shape[2], x.shape[3], pad)
 
 
-# Packed / transformed filters of a module's OWN parameters are cached per weight version: a first-order meta-iteration
-# reads them in every support and target pass (SepConv's Subnets: 11 passes) and only the outer optimizer step changes them.
-# The cache is a dict OWNED BY THE MODULE (MetaConv2dLayer passes its own): it dies with the module, so a parameter of a later
-# module that happens to reuse the address can never alias an entry.  Fast weights are new tensors every inner step and are
-# never cached.  Nothing is looked up or stored while a hipGraph is being captured (a replay must recompute the filters from
-# the live weights).
-_FILTER_CACHE_PER_MODULE = 6
-
-
-def _filters(kind, weight, fwd, bwd, cache):
-    make = convk_filters if kind == 'convk' else (conv3x3_filters if kind == 'wino' else (lambda w_, f_, b_: conv3x3_filters(w_, f_, b_, f2=True)))
-    if cache is None or torch.cuda.is_current_stream_capturing():
-        return make(weight, fwd, bwd)
-    key = (kind, weight.data_ptr(), weight._version, tuple(weight.shape), weight.device.index, _hip.current_stream())
-    hit = cache.get(key)
-    if hit is not None and (hit[0] is not None or not fwd) and (hit[1] is not None or not bwd):
-        return (hit[0] if fwd else None), (hit[1] if bwd else None)
-    pf, pb = make(weight, fwd or (hit is not None and hit[0] is not None), bwd or (hit is not None and hit[1] is not None))
-    cache.pop(key, None)
-    while len(cache) >= _FILTER_CACHE_PER_MODULE:
-        cache.pop(next(iter(cache)))
-    cache[key] = (pf, pb)
-    return (pf if fwd else None), (pb if bwd else None)
-
-
 def conv3x3_eligible(x, weight, stride, padding, dilation, groups, backward=False):
     """Do the Winograd thresholds admit this shared-weight layer (whatever the direct kernel says of it)?"""
     layer = _layer_of(x, weight, stride, padding, dilation, groups)
@@ -1172,11 +1147,11 @@ def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct
         "unit-major output: Winograd route (not the F(2x2) form of a small launch), no activation"
     ctx.u_bwd = None
     if route.fwd == 'convk':
-        u_fwd, ctx.u_bwd = _filters('convk', w, True, need_x, cache)
+        u_fwd, ctx.u_bwd = filter_lookup('convk', w, True, need_x, cache)
         z = convk_tasks_pre(x, u_fwd, T or 1, Ci, Co, K, b, 0, slope, pad, direct, reflect)
     elif route.fwd in ('wino', 'wino2'):
         # both filter transforms of this layer in one launch: the data gradient of the same step will want the other one
-        u_fwd, ctx.u_bwd = _filters(route.fwd, w, True, need_x and route.dgrad == route.fwd, cache)
+        u_fwd, ctx.u_bwd = filter_lookup(route.fwd, w, True, need_x and route.dgrad == route.fwd, cache)
         z = conv3x3_tasks_pre(x, u_fwd, T or 1, Ci, Co, b, 0, slope, pad, out_unit16=bool(out_unit16), f2=route.fwd == 'wino2')
     else:
         z = _aten_conv(x, w, stride, padding, dilation, groups, T)
@@ -1222,7 +1197,7 @@ def _conv_backward(ctx, gy):
         if not need_x:
             return None, None, None
         if u_bwd is None:
-            u_bwd = _filters('wino', w, False, True, None)[1]
+            u_bwd = filter_lookup('wino', w, False, True, None)[1]
         return conv3x3_dgrad_in_unit16(gy, u_bwd, T, Ci, Co, pad), None, None
     identity = slope == 1.0 or ctx.defer     # no activation, or its derivative already applied by the consumer: gz is gy itself,
     gz = gy if identity else torch.empty_like(gy)        # only the bias gradient is computed
@@ -1251,7 +1226,7 @@ def _conv_backward(ctx, gy):
     gx = gw = None
     if need_x and route.dgrad == 'convk':
         if u_bwd is None:
-            u_bwd = _filters('convk', w, False, True, ctx.cache)[1]
+            u_bwd = filter_lookup('convk', w, False, True, ctx.cache)[1]
         if ctx.reflect:     # gradient of the mirrored (padded) extent = the full data gradient of the unpadded convolution, folded
             gx = reflect_pad_bwd(convk_tasks_pre(gz, u_bwd, tasks, Ci, Co, K, None, 1, 1.0, 0, direct), pad)
         else:
@@ -1370,31 +1345,213 @@ def conv3x3_tasks(x, weight, bias=None, mode=0, slope=1.0, pad=1, f2=False):
 
 
 # --------------------------------------------------------------------------------------------
-# Filters of every layer in ONE launch per inner step.
+# The filter store: where a fused convolution gets its packed ('convk') or Winograd-transformed ('wino', 'wino2') filters from.
 #
-# The fused kernels read a fast weight through a packed (convk) or Winograd-transformed (wino) copy, made per layer and pass: 270
-# launches of ~9 us in a SepConv meta-iteration, 760 in a CAIN one (profiles/r03_*_one_iteration.txt).  The fast weights of a step
-# are born together in mt_update: the first step records which of its outputs were packed, and how (the "plan" of that list of
-# shapes); from then on every update packs those outputs straight away with savfi_*_filters_multi_f32, and convk_filters /
-# conv3x3_filters find the result.  An entry keeps its weight tensor alive, so a data pointer cannot come back as another tensor
-# while the entry exists; the weight's version is part of the match.
+# The fused kernels read a weight through such a copy; made per layer and pass that is 270 launches of ~9 us in a SepConv meta-iteration,
+# 760 in a CAIN one (profiles/r03_*_one_iteration.txt).  filter_lookup therefore asks three stores before it launches:
+#   the module's cache: a module's OWN parameter is read in every support and target pass of a first-order meta-iteration (SepConv's
+#     Subnets: 11 passes) and only the outer optimizer step changes it.  The dict is OWNED BY THE MODULE (MetaConv2dLayer passes its own):
+#     it dies with the module, so a parameter of a later module that happens to reuse the address can never alias an entry.
+#     refresh_module_filters re-makes the entries of all modules after that step in one launch per kind.
+#   the prepacked filters: the fast weights of a step are born together in an update (mt_update, mt_scale).  The first step records which
+#     of its outputs were packed, and how (the "plan" of that list of shapes); from then on every update packs those outputs straight away
+#     with one launch per kind (filters_after_update).  An entry keeps its weight tensor alive, so a data pointer cannot come back as another
+#     tensor while the entry exists; the weight's version is part of the match.
+#   the constant weights: long-lived tensors that are no module's parameter (sepconv/model.py: the four sub-networks' own parameters
+#     stacked into one task-batched layer; rebuilt when a parameter changes) are registered, and their filters are made once per tensor,
+#     kind and stream.  Keyed on the data pointer of a tensor the registry keeps alive, so the pointer cannot be recycled meanwhile.
+# While a hipGraph is captured, filters that live outside the capture are neither read nor stored: a replay runs no Python, so it must
+# recompute the filters from the live weights (a kernel captured on a cached filter would read the transform of an old weight after the
+# next in-place step).  The module's cache and the constant weights skip while capturing.  The prepacked filters and the plan do not:
+# graph_inner_loop calls filters_after_update INSIDE the capture, so the many-layer launch and the convolutions that read its slices are
+# nodes of one graph.  The state is shared by the per-task threads of --task_streams (a key that holds device memory names its stream).
 # --------------------------------------------------------------------------------------------
 PREPACK = True
-_pack_plans = {}        # tuple of the update's weight shapes -> {index: [kind, fwd, bwd]}
-_last_update = None     # (signature, {data_ptr: index}, outputs) of the newest update
-_prepacked = {}         # (kind, data_ptr) -> (weight, version, filters_fwd, filters_bwd)
+_FILTER_CACHE_PER_MODULE = 6
+_CONST_WEIGHTS_MAX = 64     # a model that goes away without unregistering leaves its entries behind: oldest out (16 per SepConv net and stream)
+_pack_plans = {}            # tuple of the update's weight shapes -> {index: [kind, fwd, bwd]}
+_last_update = None         # (signature, {data_ptr: index}, outputs) of the newest update
+_prepacked = {}             # (kind, data_ptr) -> (weight, version, filters_fwd, filters_bwd)
+_const_weights = {}         # data_ptr -> [weight, version, {(kind, stream): [filters_fwd, filters_bwd]}]
+_const_weights_lock = threading.Lock()      # --task_streams: the per-task Python threads register / evict concurrently
+
+# what the store asks of the process, through these names at call time (a host test puts its own in their place)
+_on_device, _capturing, _raw_stream = (lambda t: t.is_cuda), torch.cuda.is_current_stream_capturing, _hip.current_stream
+
+# One descriptor per kind, in the order the many-layer launches are issued.  form: None for the direct kernel's packed bf16 triples, whose
+# entry points take K where those of the Winograd transforms take the form (bit 1 of the C ABI's `mode`; 0: by the library's channel rule,
+# 2: F(2x2) whatever the channel counts).  floats: the size query of one filter; timer: the name of the single-layer launch, with "_multi"
+# that of the many-layer launch; single, multi: their C entry points.
+FilterKind = collections.namedtuple('FilterKind', 'form floats timer single multi')
+_WINO = ("savfi_conv3x3_filter_floats", "conv3x3_filters", "savfi_conv3x3_filters_form_f32", "savfi_conv3x3_filters_multi_form_f32")
+_KINDS = {'convk': FilterKind(None, "savfi_convk_filter_floats", "convk_filters", "savfi_convk_filters_f32", "savfi_convk_filters_multi_f32"),
+          'wino': FilterKind(0, *_WINO), 'wino2': FilterKind(2, *_WINO)}
+_ptr = lambda t: None if t is None else t.data_ptr()          # (a direction that is not wanted goes to the C ABI as NULL)
 
 
 def _filter_shape(weight):
+    """(T, Co, Ci, K) of a weight [Co,Ci,K,K] (T = 1) or [T,Co,Ci,K,K]."""
     T, Co, Ci = (1,) + tuple(weight.shape[:2]) if weight.dim() == 4 else tuple(weight.shape[:3])
     return int(T), int(Co), int(Ci), int(weight.shape[-1])
 
 
+def _filter_floats(k, T, Ci, Co, K, mode):
+    """Floats of one filter of kind k; mode 0: forward, 1: data gradient."""
+    return _workspace_floats(k.floats, T, Ci, Co, *((K, mode) if k.form is None else (mode | k.form,)))
+
+
+def _make_filters(kind, weight, fwd, bwd):
+    """The single-layer launch: (filters_fwd, filters_bwd) of `weight`, both in ONE launch; None where not wanted."""
+    k = _KINDS[kind]
+    T, Co, Ci, K = _filter_shape(weight)
+    us = [torch.empty(_filter_floats(k, T, Ci, Co, K, mode), dtype=torch.float32, device=weight.device) if want else None
+          for mode, want in ((0, fwd), (1, bwd))]
+    entry, arg = getattr(_hip.lib(), k.single), (K if k.form is None else k.form)
+    _hip.launch(k.timer, lambda: _hip.check(entry(weight.data_ptr(), _ptr(us[0]), _ptr(us[1]), T, Ci, Co, arg, _raw_stream()), k.single))
+    return us[0], us[1]
+
+
+def _filters_multi(kind, jobs):
+    """The many-layer launch: [(weight, want_fwd, want_bwd)] -> [(filters_fwd, filters_bwd)] with ONE launch per 56 (layer, mode) jobs; the
+    results are slices of one buffer, each rounded up to 64 floats (256-byte aligned)."""
+    if not jobs:
+        return []
+    k, n = _KINDS[kind], len(jobs)
+    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
+    pw, pf, pb = PA(), PA(), PA()
+    aT, aCi, aCo, aK = IA(), IA(), IA(), IA()
+    cuts, total = [], 0
+    for j, (w, f, b) in enumerate(jobs):
+        T, Co, Ci, K = aT[j], aCo[j], aCi[j], aK[j] = _filter_shape(w)
+        nf, nb = ((_filter_floats(k, T, Ci, Co, K, mode) + 63) // 64 * 64 if want else 0 for mode, want in ((0, f), (1, b)))
+        cuts.append((total, total + nf, total + nf + nb))
+        total += nf + nb
+    flat = torch.empty(total, dtype=torch.float32, device=jobs[0][0].device)
+    made = []
+    for j, ((w, _, _), (start, mid, end)) in enumerate(zip(jobs, cuts)):
+        tf, tb = (flat[start:mid] if mid > start else None), (flat[mid:end] if end > mid else None)
+        pw[j], pf[j], pb[j] = w.data_ptr(), _ptr(tf), _ptr(tb)
+        made.append((tf, tb))
+    entry, arg = getattr(_hip.lib(), k.multi), (aK if k.form is None else IA(*([k.form] * n)))
+    _hip.launch(k.timer + "_multi", lambda: _hip.check(entry(pw, pf, pb, aT, aCi, aCo, arg, n, _raw_stream()), k.multi))
+    return made
+
+
+_ModuleKey = collections.namedtuple('_ModuleKey', 'kind ptr version shape device stream')
+
+
+def _module_key(kind, weight):
+    """The key of a module's cache (a plain tuple: it is built on every lookup; _ModuleKey names its fields)."""
+    return (kind, weight.data_ptr(), weight._version, tuple(weight.shape), weight.device.index, _raw_stream())
+
+
+def filter_lookup(kind, weight, fwd, bwd, cache=None):
+    """(filters_fwd, filters_bwd) of `weight` ([Co,Ci,K,K] or [T,Co,Ci,K,K]) for the kernels of `kind`; an entry is None when not asked
+    for.  `cache`: the dict of the module whose own parameter `weight` is, None for every other weight.  The first level that answers wins:
+
+    1. The module's cache -- only with `cache`, and not while capturing.  Keyed (kind, data pointer, version, shape, device, stream), at
+       most _FILTER_CACHE_PER_MODULE entries, oldest out.  An entry that lacks a wanted direction is made again by the levels below with
+       the wanted directions plus those it held, and becomes the newest; only the wanted directions are returned.
+    2. The prepacked filters of the newest update -- keyed (kind, data pointer); a hit needs the same version, the same shape and EVERY
+       wanted direction, else it is a miss.  Also while capturing (see above).
+    3. The registered constant weights -- not while capturing.  An entry is valid for the version and shape it was registered with; its
+       filters are kept per (kind, stream), only the missing directions are made, both are kept.
+    4. A single-layer launch.  If the weight is an output of the newest update, the plan of that update learns it first."""
+    wanted, key = (fwd, bwd), None
+    if cache is not None and not _capturing():                                      # 1
+        key = _module_key(kind, weight)
+        hit = cache.get(key)
+        if hit is not None:
+            if (hit[0] is not None or not fwd) and (hit[1] is not None or not bwd):
+                return (hit[0] if fwd else None), (hit[1] if bwd else None)
+            fwd, bwd = fwd or hit[0] is not None, bwd or hit[1] is not None
+    weight = weight.contiguous()
+    _hip.require_cuda(weight)
+    assert weight.shape[-2] == weight.shape[-1] and (kind == 'convk' or weight.shape[-1] == 3) and (fwd or bwd), (kind, weight.shape)
+    made = _prepacked_filters(kind, weight, fwd, bwd)                               # 2
+    if made is None:
+        made = _const_filters(kind, weight, fwd, bwd)                               # 3
+    if made is None:
+        _learn_plan(kind, weight, fwd, bwd)                                         # 4
+        made = _make_filters(kind, weight, fwd, bwd)
+    if key is not None:
+        cache.pop(key, None)
+        while len(cache) >= _FILTER_CACHE_PER_MODULE:
+            cache.pop(next(iter(cache)))
+        cache[key] = made
+    return (made[0] if wanted[0] else None), (made[1] if wanted[1] else None)
+
+
+def convk_filters(weight, fwd=True, bwd=True):
+    """savfi_convk_filters_f32: weight [T,Co,Ci,K,K] (or [Co,Ci,K,K]) packed as bf16 triples in MFMA fragment order for the
+    forward pass and / or the data gradient of the direct K x K convolution, in one call.  Returns (p_fwd, p_bwd)."""
+    return filter_lookup('convk', weight, fwd, bwd)
+
+
+def conv3x3_filters(weight, fwd=True, bwd=True, f2=False):
+    """savfi_conv3x3_filters_form_f32: the Winograd transforms of weight [T,Co,Ci,3,3] (or [Co,Ci,3,3]) for the forward pass and / or
+    the data gradient, in ONE launch.  Returns (u_fwd, u_bwd); an entry is None when not asked for.  f2: the F(2x2) form whatever the
+    channel counts (kind 'wino2': wino_form2) -- such filters go with conv3x3_tasks_pre(..., f2=True) only."""
+    return filter_lookup('wino2' if f2 else 'wino', weight, fwd, bwd)
+
+
+def _prepacked_filters(kind, weight, fwd, bwd):
+    hit = _prepacked.get((kind, weight.data_ptr())) if _prepacked else None
+    if hit is None or hit[1] != weight._version or hit[0].shape != weight.shape or (fwd and hit[2] is None) or (bwd and hit[3] is None):
+        return None
+    return (hit[2] if fwd else None), (hit[3] if bwd else None)
+
+
+def _const_filters(kind, weight, fwd, bwd):
+    e = _const_weights.get(weight.data_ptr()) if _const_weights else None
+    if e is None or e[1] != weight._version or e[0].shape != weight.shape or _capturing():
+        return None
+    have = e[2].setdefault((kind, _raw_stream()), [None, None])
+    need_f, need_b = fwd and have[0] is None, bwd and have[1] is None
+    if need_f or need_b:
+        pf, pb = _make_filters(kind, weight, need_f, need_b)
+        if need_f:
+            have[0] = pf
+        if need_b:
+            have[1] = pb
+    return (have[0] if fwd else None), (have[1] if bwd else None)
+
+
+def _learn_plan(kind, weight, fwd, bwd):
+    """A layer makes its own filters from `weight`: if that is an output of the newest update, the plan of that update learns it.  The
+    first kind seen for an output stays; directions are added for that kind only."""
+    if _last_update is None:
+        return
+    sig, index, _ = _last_update
+    i = index.get(weight.data_ptr())
+    if i is None or tuple(weight.shape) != sig[i]:
+        return
+    entry = _pack_plans.setdefault(sig, {}).get(i)
+    if entry is None:
+        _pack_plans[sig][i] = [kind, bool(fwd), bool(bwd)]
+    elif entry[0] == kind:
+        entry[1], entry[2] = entry[1] or bool(fwd), entry[2] or bool(bwd)
+
+
+def register_const_weight(w):
+    with _const_weights_lock:
+        while len(_const_weights) >= _CONST_WEIGHTS_MAX:
+            _const_weights.pop(next(iter(_const_weights)), None)
+        _const_weights[w.data_ptr()] = [w, w._version, {}]
+    return w
+
+
+def unregister_const_weight(w):
+    with _const_weights_lock:
+        _const_weights.pop(w.data_ptr(), None)
+
+
 def filters_after_update(outs):
-    """Called with the fast weights an update just produced: pack / transform the ones the plan of this list names."""
+    """Called with the fast weights an update just produced: pack / transform the ones the plan of this list names, one many-layer
+    launch per kind.  What the previous update prepared is dropped in any case."""
     global _last_update
     _prepacked.clear()
-    if not PREPACK or not outs or not outs[0].is_cuda:
+    if not PREPACK or not outs or not _on_device(outs[0]):
         _last_update = None
         return
     sig = tuple(tuple(o.shape) for o in outs)
@@ -1402,77 +1559,34 @@ def filters_after_update(outs):
     plan = _pack_plans.get(sig)
     if not plan:
         return
-    for kind in ('convk', 'wino', 'wino2'):
+    for kind in _KINDS:
         jobs = [(outs[i], e[1], e[2]) for i, e in sorted(plan.items()) if e[0] == kind]
         for (w, _, _), (tf, tb) in zip(jobs, _filters_multi(kind, jobs)):
             _prepacked[(kind, w.data_ptr())] = (w, w._version, tf, tb)
 
 
-def _filters_multi(kind, jobs):
-    """[(weight, want_fwd, want_bwd)] -> [(filters_fwd, filters_bwd)] with ONE launch per 56 (layer, mode) jobs; the results are
-    slices of one buffer."""
-    if not jobs:
-        return []
-    lib = _hip.lib()
-    dev = jobs[0][0].device
-    sizes, total = [], 0
-    for w, f, b in jobs:
-        T, Co, Ci, K = _filter_shape(w)
-        if kind == 'convk':
-            nf = _workspace_floats("savfi_convk_filter_floats", T, Ci, Co, K, 0) if f else 0
-            nb = _workspace_floats("savfi_convk_filter_floats", T, Ci, Co, K, 1) if b else 0
-        else:
-            fbit = 2 if kind == 'wino2' else 0
-            nf = _workspace_floats("savfi_conv3x3_filter_floats", T, Ci, Co, 0 | fbit) if f else 0
-            nb = _workspace_floats("savfi_conv3x3_filter_floats", T, Ci, Co, 1 | fbit) if b else 0
-        nf, nb = (nf + 63) // 64 * 64, (nb + 63) // 64 * 64          # 256-byte aligned slices
-        sizes.append((total, nf, total + nf, nb))
-        total += nf + nb
-    flat = torch.empty(total, dtype=torch.float32, device=dev)
-    n = len(jobs)
-    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    pw, pf, pb = PA(), PA(), PA()
-    aT, aCi, aCo, aK = IA(), IA(), IA(), IA()
-    made = []
-    for k, ((w, f, b), (of, nf, ob, nb)) in enumerate(zip(jobs, sizes)):
-        T, Co, Ci, K = _filter_shape(w)
-        tf = flat[of:of + nf] if nf else None
-        tb = flat[ob:ob + nb] if nb else None
-        pw[k], pf[k], pb[k] = w.data_ptr(), (tf.data_ptr() if nf else None), (tb.data_ptr() if nb else None)
-        aT[k], aCi[k], aCo[k], aK[k] = T, Ci, Co, K
-        made.append((tf, tb))
-    if kind == 'convk':
-        _hip.launch("convk_filters_multi", lambda: _hip.check(lib.savfi_convk_filters_multi_f32(
-            pw, pf, pb, aT, aCi, aCo, aK, n, _hip.current_stream()), "savfi_convk_filters_multi_f32"))
-    else:
-        aF = IA(*([2 if kind == 'wino2' else 0] * n))
-        _hip.launch("conv3x3_filters_multi", lambda: _hip.check(lib.savfi_conv3x3_filters_multi_form_f32(
-            pw, pf, pb, aT, aCi, aCo, aF, n, _hip.current_stream()), "savfi_conv3x3_filters_multi_form_f32"))
-    return made
-
-
 def refresh_module_filters(modules):
     """After an in-place update of the modules' OWN weights (the outer optimizer step): re-make, in one launch per kind, the
     filters each module's cache holds for the previous version of its weight (CAIN: 500 single-layer packs per meta-iteration)."""
-    if not PREPACK or torch.cuda.is_current_stream_capturing():
+    if not PREPACK or _capturing():
         return
-    st = _hip.current_stream()
-    jobs = {'convk': [], 'wino': [], 'wino2': []}
+    st = _raw_stream()
+    jobs = {kind: [] for kind in _KINDS}
     for m in modules:
         cache, w = getattr(m, '_filters', None), getattr(m, 'weight', None)
-        if not cache or w is None or not w.is_cuda or not w.is_contiguous():
+        if not cache or w is None or not _on_device(w) or not w.is_contiguous():
             continue
-        for key in reversed(list(cache)):
-            kind, ptr, ver, shape, dev, stream = key
-            if ptr == w.data_ptr() and shape == tuple(w.shape) and stream == st:
-                if ver != w._version:
+        for key in reversed(list(cache)):           # the newest entry of this weight on this stream, if it is of another version
+            k = _ModuleKey(*key)
+            if k.ptr == w.data_ptr() and k.shape == tuple(w.shape) and k.stream == st:
+                if k.version != w._version:
                     old = cache[key]
-                    jobs[kind].append((m, key, (w.detach(), old[0] is not None, old[1] is not None)))
+                    jobs[k.kind].append((m, key, (w.detach(), old[0] is not None, old[1] is not None)))
                 break
     for kind, items in jobs.items():
         for (m, key, (w, _, _)), made in zip(items, _filters_multi(kind, [it[2] for it in items])):
             m._filters.pop(key, None)
-            m._filters[(kind, w.data_ptr(), w._version, tuple(w.shape), w.device.index, st)] = made
+            m._filters[_module_key(kind, w)] = made
 
 
 # Memory-layout tags.  Two tensors of the SepConv tail keep the shape [4N, 51, H, W] while their MEMORY is unit-major, [H][W / 16][51][16]
@@ -1501,95 +1615,6 @@ def require_layout(t, layout, what):
 
 class SavfiLayoutError(RuntimeError):
     pass
-
-
-# Long-lived constant weights (sepconv/model.py: the four sub-networks' own parameters stacked into one task-batched layer; rebuilt when a
-# parameter changes): their packed / transformed filters are made once per tensor, whichever function asks.  Keyed on the data pointer of a
-# tensor the registry keeps alive, so the pointer cannot be recycled while the entry exists.
-_const_weights = {}
-_const_weights_lock = threading.Lock()      # --task_streams: the per-task Python threads register / evict concurrently
-
-
-_CONST_WEIGHTS_MAX = 64         # a model that goes away without unregistering leaves its entries behind: oldest out (16 per SepConv net and stream)
-
-
-def register_const_weight(w):
-    with _const_weights_lock:
-        while len(_const_weights) >= _CONST_WEIGHTS_MAX:
-            _const_weights.pop(next(iter(_const_weights)), None)
-        _const_weights[w.data_ptr()] = [w, w._version, {}]
-    return w
-
-
-def unregister_const_weight(w):
-    with _const_weights_lock:
-        _const_weights.pop(w.data_ptr(), None)
-
-
-def _const_filters(kind, weight, fwd, bwd, make):
-    """(filters_fwd, filters_bwd) of a registered constant weight (made on first use by `make(fwd, bwd)`), or None."""
-    e = _const_weights.get(weight.data_ptr()) if _const_weights else None
-    if e is None or e[1] != weight._version or e[0].shape != weight.shape or torch.cuda.is_current_stream_capturing():
-        return None
-    have = e[2].setdefault((kind, _hip.current_stream()), [None, None])
-    need_f, need_b = fwd and have[0] is None, bwd and have[1] is None
-    if need_f or need_b:
-        pf, pb = make(need_f, need_b)
-        if need_f:
-            have[0] = pf
-        if need_b:
-            have[1] = pb
-    return (have[0] if fwd else None), (have[1] if bwd else None)
-
-
-def _prepacked_filters(kind, weight, fwd, bwd):
-    hit = _prepacked.get((kind, weight.data_ptr())) if _prepacked else None
-    if hit is None or hit[1] != weight._version or hit[0].shape != weight.shape or (fwd and hit[2] is None) or (bwd and hit[3] is None):
-        return None
-    return (hit[2] if fwd else None), (hit[3] if bwd else None)
-
-
-def _note_filter_use(kind, weight, fwd, bwd):
-    """A layer made its own filters from `weight`: if that is an output of the newest update, the plan of that update learns it."""
-    if _last_update is None:
-        return
-    sig, index, _ = _last_update
-    i = index.get(weight.data_ptr())
-    if i is None or tuple(weight.shape) != sig[i]:
-        return
-    entry = _pack_plans.setdefault(sig, {}).get(i)
-    if entry is None:
-        _pack_plans[sig][i] = [kind, bool(fwd), bool(bwd)]
-    elif entry[0] == kind:
-        entry[1], entry[2] = entry[1] or bool(fwd), entry[2] or bool(bwd)
-
-
-def conv3x3_filters(weight, fwd=True, bwd=True, f2=False):
-    """savfi_conv3x3_filters_form_f32: the Winograd transforms of weight [T,Co,Ci,3,3] (or [Co,Ci,3,3]) for the forward pass and / or
-    the data gradient, in ONE launch.  Returns (u_fwd, u_bwd); an entry is None when not asked for.  f2: the F(2x2) form whatever the
-    channel counts (kind 'wino2': wino_form2) -- such filters go with conv3x3_tasks_pre(..., f2=True) only."""
-    kind, fbit = ('wino2', 2) if f2 else ('wino', 0)
-    weight = weight.contiguous()
-    _hip.require_cuda(weight)
-    T, Co, Ci = (1,) + tuple(weight.shape[:2]) if weight.dim() == 4 else tuple(weight.shape[:3])
-    assert tuple(weight.shape[-2:]) == (3, 3) and (fwd or bwd), weight.shape
-    ready = _prepacked_filters(kind, weight, fwd, bwd)
-    if ready is not None:
-        return ready
-
-    def make(fwd, bwd):
-        lib = _hip.lib()
-        us = [torch.empty(_workspace_floats("savfi_conv3x3_filter_floats", T, Ci, Co, mode | fbit), dtype=weight.dtype, device=weight.device) if want else None
-              for mode, want in ((0, fwd), (1, bwd))]
-        _hip.launch("conv3x3_filters", lambda: _hip.check(lib.savfi_conv3x3_filters_form_f32(
-            weight.data_ptr(), None if us[0] is None else us[0].data_ptr(), None if us[1] is None else us[1].data_ptr(), T, Ci, Co, fbit,
-            _hip.current_stream()), "savfi_conv3x3_filters_form_f32"))
-        return us[0], us[1]
-    ready = _const_filters(kind, weight, fwd, bwd, make)
-    if ready is not None:
-        return ready
-    _note_filter_use(kind, weight, fwd, bwd)
-    return make(fwd, bwd)
 
 
 def conv3x3_unit16_supported(x, w, pad):
@@ -1703,33 +1728,6 @@ class _MaskGrad(torch.autograd.Function):
 
 def mask_grad(x, slope):
     return _MaskGrad.apply(x, float(slope))
-
-
-def convk_filters(weight, fwd=True, bwd=True):
-    """savfi_convk_filters_f32: weight [T,Co,Ci,K,K] (or [Co,Ci,K,K]) packed as bf16 triples in MFMA fragment order for the
-    forward pass and / or the data gradient of the direct K x K convolution, in one call.  Returns (p_fwd, p_bwd)."""
-    weight = weight.contiguous()
-    _hip.require_cuda(weight)
-    T, Co, Ci = (1,) + tuple(weight.shape[:2]) if weight.dim() == 4 else tuple(weight.shape[:3])
-    K = int(weight.shape[-1])
-    assert weight.shape[-2] == K and (fwd or bwd), weight.shape
-    ready = _prepacked_filters('convk', weight, fwd, bwd)
-    if ready is not None:
-        return ready
-
-    def make(fwd, bwd):
-        lib = _hip.lib()
-        ps = [torch.empty(_workspace_floats("savfi_convk_filter_floats", T, Ci, Co, K, mode), dtype=torch.float32, device=weight.device)
-              if want else None for mode, want in ((0, fwd), (1, bwd))]
-        _hip.launch("convk_filters", lambda: _hip.check(lib.savfi_convk_filters_f32(
-            weight.data_ptr(), None if ps[0] is None else ps[0].data_ptr(), None if ps[1] is None else ps[1].data_ptr(), T, Ci, Co, K,
-            _hip.current_stream()), "savfi_convk_filters_f32"))
-        return ps[0], ps[1]
-    ready = _const_filters('convk', weight, fwd, bwd, make)
-    if ready is not None:
-        return ready
-    _note_filter_use('convk', weight, fwd, bwd)
-    return make(fwd, bwd)
 
 
 def convk_tasks_pre(x, packed, T, Ci, Co, K, bias=None, mode=0, slope=1.0, pad=1, precise=False, reflect=False, mask=None, mask_slope=1.0):

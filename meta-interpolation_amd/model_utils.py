@@ -190,7 +190,7 @@ class MetaConv2dLayer(nn.Module):
         # direct = True: a 3x3 layer of a network that amplifies Winograd rounding (VoxelFlow) asks for the direct split-bf16
         # convolution whatever its size; 5x5 / 7x7 layers take it anyway (hip_ops.convk_eligible)
         self.direct = bool(direct)
-        self._filters = {}          # packed / transformed filters of self.weight (hip_ops._filters)
+        self._filters = {}          # packed / transformed filters of self.weight (hip_ops.filter_lookup)
         self.stride, self.padding = int(stride), int(padding)
         self.dilation_rate, self.groups, self.use_bias = int(dilation_rate), int(groups), use_bias
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
