@@ -21,6 +21,7 @@
  *   savfi_mt_scale_f32         gamma_i * w_i (L2F attenuation)        meta_learning_system.py:267-268
  *   savfi_l1_mse_f32           nn.L1Loss / nn.MSELoss                 loss.py:287-290
  *   savfi_ssim_loss_f32        pytorch_msssim.SSIM as Loss constructs it, forward and gradient   loss.py:294, pytorch_msssim/__init__.py:7-131
+ *   savfi_psnr_ssim_f32        utils.quantize + calc_psnr's squared error + ssim(val_range=255), `rows` image pairs per call   utils.py:171-204, pytorch_msssim/__init__.py:19-75
  *   savfi_upsample2x_fwd/bwd_f32  bilinear x2 up-sampling                 sepconv/model.py:191,213-234; voxel_flow.py:400-414
  *   savfi_upsample2x_window_fwd/bwd_f32  the same map on a window (SepConv Subnets on the frame area)  sepconv/model.py:309-349
  *   savfi_bias_act_fwd/bwd_f32 conv bias add + (Leaky)ReLU and their backward + bias gradient
@@ -36,6 +37,7 @@
  *                                                                     superslomo/model.py:547-646 (7x7 / 5x5), model_utils.py:308-366
  *   savfi_ca_pool/mlp_fwd/mlp_bwd/apply_f32   channel attention + residual of CAIN's RCAB   model_utils.py:931-953, :957-990
  *   savfi_frames_u8_to_f32     HWC uint8 frames -> normalised fp32 NCHW  data/vimeo_septuplet.py:68-80, data/video.py:44-51
+ *   savfi_frames_f32_to_u8     unit-range fp32 NCHW -> quantised uint8 NHWC (what save_image writes)   utils.py:171-172, :276-285
  *   savfi_*_workspace_floats / savfi_bias_act_scratch_floats: sizes of the caller-owned scratch buffers (return int64_t)
  *
  * Conventions (all functions):
@@ -57,7 +59,7 @@
 extern "C" {
 #endif
 
-#define SAVFI_ABI_VERSION 22
+#define SAVFI_ABI_VERSION 23
 
 #define SAVFI_OK            0
 #define SAVFI_E_NULL       (-1)  /* a required pointer is NULL                          */
@@ -326,6 +328,23 @@ int savfi_ssim_loss_bwd_f32(const float* sr, const float* hr, const float* g_los
                             int rows, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * PSNR / SSIM evaluation metric (csrc/ssim.hip; utils.py:171-204 quantize + calc_psnr + ssim(val_range=255)), `rows` image pairs
+ * per call, two launches (tile kernel, finish), no atomics, no cleared memory, no host read: capturable and bit-reproducible.
+ *   pred, target [rows, C, H, W] in UNIT range.  Both are quantised as they are loaded, q = rint(clamp(x * 255, 0, 255)) (ties to
+ *   even, what img.mul(255).clamp(0, 255).round() gives; +-inf clamp to 255 / 0); nothing quantised is written to memory.
+ *   result[r][0] = mse  = (float)(S / (65025.0 C H W)) evaluated in double, S = sum (q_pred - q_target)^2, an exact integer
+ *                         (PSNR = -10 log10(mse + 1e-8): the caller adds the reference's epsilon)
+ *   result[r][1] = ssim = mean of the SSIM map with L = 255 (range class 2 of savfi_ssim_loss_f32: same window, same tap order,
+ *                         partial sums added in a fixed order); exactly 1.0 for an identical pair.
+ *   sq_sum[r] = S (may be NULL).  A NaN anywhere in a row makes both of that row's results NaN (and sq_sum[r] all ones).
+ *   `scratch`: savfi_psnr_ssim_scratch_bytes(rows, C, H, W) bytes, 4-byte aligned, caller-owned.
+ *   H, W >= 11, SAVFI_E_SHAPE otherwise; rows * C <= 65535 and H * W < 2^31, SAVFI_E_TOOBIG otherwise.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_psnr_ssim_scratch_bytes(int rows, int C, int H, int W);
+int savfi_psnr_ssim_f32(const float* pred, const float* target, float* result, unsigned long long* sq_sum, void* scratch,
+                        int rows, int C, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:
  *   z <- act(z + bias[c]),  act(x) = x > 0 ? x : slope*x   (slope 0 ReLU, 0.2 LeakyReLU, 1 bias only)
  * bwd: gz = gy * act'(y) with y the forward OUTPUT (sign(y) == sign(z+b) for slope >= 0);
@@ -580,6 +599,14 @@ int savfi_sub_mean_f32(const float* x, float* out, float* mean, float* workspace
  * ---------------------------------------------------------------------------------- */
 int savfi_frames_u8_to_f32(const unsigned char* src, float* dst, int64_t N, int H, int W, int swap_rb, float div,
                            float mean_c0, float mean_c1, float mean_c2, float std, void* stream);
+
+/* ----------------------------------------------------------------------------------
+ * Frame writer (utils.py:276-285 save_image, :171-172 quantize): src fp32 [N,C,H,W] in unit range ->
+ * dst[n][y][x][c] = rint(clamp(src[n][c][y][x] * 255, 0, 255)) as uint8 [N,H,W,C] on the DEVICE, so that a frame leaves it as
+ * bytes.  The same quantisation as savfi_psnr_ssim_f32 (one device function); a NaN is written as 0.  C = 1 or 3,
+ * SAVFI_E_UNSUPPORTED otherwise.
+ * ---------------------------------------------------------------------------------- */
+int savfi_frames_f32_to_u8(const float* src, unsigned char* dst, int64_t N, int C, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ RULE_SGD, RULE_ADAM, RULE_ADAMAX_LSLR, RULE_ADAMAX_MSGD = 0, 1, 2, 3
 LR_SCALAR, LR_ELEMENT = 0, 1
 SSIM_RANGE_PER_ROW, SSIM_RANGE_BATCH, SSIM_RANGE_FIXED = 0, 1, 2
 SEPCONV_PARTITION_WS, SEPCONV_PARTITION_X6, SEPCONV_PARTITION_FP32 = 0, 1, 2
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _ERRORS = {-1: "SAVFI_E_NULL (a required pointer is NULL)",
            -2: "SAVFI_E_SHAPE (bad or inconsistent dimension)",
@@ -77,6 +77,8 @@ _PROTOTYPES = {
     "savfi_ssim_scratch_floats": [c_int, c_int, c_int, c_int],
     "savfi_ssim_loss_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_ssim_loss_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "savfi_psnr_ssim_scratch_bytes": [c_int, c_int, c_int, c_int],
+    "savfi_psnr_ssim_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_fwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_bwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_workspace_floats": [c_int] * 7,
@@ -126,6 +128,7 @@ _PROTOTYPES = {
     "savfi_sub_mean_workspace_floats": [c_int64, c_int],
     "savfi_sub_mean_f32": [_P, _P, _P, _P, c_int64, c_int, _P],
     "savfi_frames_u8_to_f32": [_P, _P, c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, _P],
+    "savfi_frames_f32_to_u8": [_P, _P, c_int64, c_int, c_int, c_int, _P],
     "savfi_upsample2x_window_fwd_f32": [_P, _P] + [c_int] * 12 + [_P],
     "savfi_upsample2x_window_bwd_f32": [_P, _P] + [c_int] * 12 + [_P],
     "savfi_upsample2x_window_bwd_masked_f32": [_P, _P, c_float, _P] + [c_int] * 12 + [_P],
@@ -163,7 +166,7 @@ def lib():
         except AttributeError:
             raise SavfiHipError("%s does not export %s" % (LIB_PATH, name))
         fn.argtypes = argtypes
-        fn.restype = c_int64 if name.endswith(('_floats', '_workgroups')) else c_int
+        fn.restype = c_int64 if name.endswith(('_floats', '_workgroups', '_bytes')) else c_int
     got = handle.savfi_version()
     if got != ABI_VERSION:
         raise SavfiHipError("libsavfi_hip ABI %d != expected %d; rebuild" % (got, ABI_VERSION))

@@ -49,6 +49,15 @@ __device__ __forceinline__ float block_sum(float x, float* lds /* >= NW floats *
   return t;
 }
 
+// utils.quantize(img, 1.) of a unit-range value: img.mul(255).clamp(0, 255).round() -- one fp32 multiply, a clamp that lets NaN
+// through as torch.clamp does (fminf / fmaxf would drop it; +-inf go to 255 / 0), ties to even.  The integers of the PSNR / SSIM
+// metric (csrc/ssim.hip) and the bytes of a written frame (csrc/frames.hip) both come from here.
+__device__ __forceinline__ float savfi_quantize255(float x) {
+  const float v = x * 255.f;
+  const float c = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+  return rintf(c);
+}
+
 // csrc/sepconv_x6.hip: gV and gH of the K = 51, C = 3 separable convolution on split-bf16 MFMAs (internal: reached through
 // savfi_sepconv_bwd_f32)
 int savfi_sepconv_bwd_x6_launch(const float* in, const float* v, const float* h, const float* gO, float* gV, float* gH, int B, int Ho,

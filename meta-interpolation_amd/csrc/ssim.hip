@@ -17,6 +17,11 @@
 //                  d loss / d sr = -(g / (2 n)) (G^T[a] + 2 sr G^T[b] + hr G^T[c])
 //                  b = d map / d s1, c = d map / d s12, a = (d map / d mu1 at fixed s1, s12) - 2 mu1 b - mu2 c
 //                Nothing is kept from the forward but the two images and the range word.
+// The PSNR / SSIM evaluation metric (utils.py:171-204: quantize + calc_psnr + ssim(val_range=255)) is the forward tile once more:
+//   metric_tile    fwd_tile<METRIC>: both unit-range images quantised to 0 .. 255 as they are loaded into LDS, L = 255 fixed (no range
+//                  pass, no range word), and next to the SSIM partial sum the integer sum of squared differences of the pixels the
+//                  workgroup owns
+//   metric_finish  per row: SSIM partial sums in ssim_finish's order -> mean; integer partials as 64 bits -> S, mse = S / (65025 n)
 // Every window sum is accumulated tap 0 .. 10 in the same association for every pixel, whatever its place in a tile.
 // LDS: lanes run along image columns in every pass, so each ds_read_b32 / ds_write_b32 of a wave touches consecutive
 // words (conflict-free for any row stride); 49 KB (forward) and 59 KB (backward) of static LDS: three resp. two workgroups per CU.
@@ -120,8 +125,9 @@ __global__ __launch_bounds__(NT) void ssim_range(const float* __restrict__ sr, f
 }
 
 // (ROWS x COLS) patch of a plane with origin (y0, x0) -> LDS [ROWS][COLS], zero outside the plane.  x0 % 4 == 0;
-// vec_ok: plane base 16-byte aligned and W % 4 == 0.
-template <int ROWS, int COLS>
+// vec_ok: plane base 16-byte aligned and W % 4 == 0.  QUANT: the values are quantised to 0 .. 255 on the way (the metric: LDS holds
+// the integers, nothing quantised goes to HBM); outside the plane stays 0.
+template <int ROWS, int COLS, bool QUANT = false>
 __device__ __forceinline__ void load_patch(const float* __restrict__ plane, float* __restrict__ dst, int y0, int x0, int H, int W,
                                            int vec_ok) {
   constexpr int QUADS = COLS / 4;
@@ -139,6 +145,7 @@ __device__ __forceinline__ void load_patch(const float* __restrict__ plane, floa
         if (gx + 2 >= 0 && gx + 2 < W) v.z = src[gx + 2];
         if (gx + 3 >= 0 && gx + 3 < W) v.w = src[gx + 3];
       }
+      if constexpr (QUANT) v = make_float4(savfi_quantize255(v.x), savfi_quantize255(v.y), savfi_quantize255(v.z), savfi_quantize255(v.w));
     }
     *reinterpret_cast<float4*>(dst + r * COLS + 4 * q) = v;
   }
@@ -174,10 +181,18 @@ __device__ __forceinline__ float ssim_value(const float (&m)[5], float C1, float
   return r1 * r2;
 }
 
-// grid (tiles_x, tiles_y, rows * C); partial[(z * tiles_y + by) * tiles_x + bx]
-__global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
-                                               int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word,
-                                               float* __restrict__ partial, int C, int H, int W, int vec_ok) {
+// NaN word of a workgroup's squared-error partial (a workgroup's sum stays below 2^27, see metric_tile)
+constexpr unsigned SQ_NAN = 0xffffffffu;
+
+// One forward tile, for both kernels below.  grid (tiles_x, tiles_y, rows * C); partial[(z * tiles_y + by) * tiles_x + bx].
+// METRIC: the patches are quantised on load, the range class is 2 (L = 255: no extrema, no range word), and the workgroup also adds
+// (q_p - q_t)^2 as an integer over the pixels it owns -> sq_partial (same index).  Every pixel of the plane has one owner: the
+// tiles step over the SSIM positions, so the last tile row / column also own the 10 trailing pixel rows / columns, which lie
+// inside their patch (<= 26 x 74 pixels * 65025 < 2^27: the 32-bit sum is exact).  A NaN among the owned pixels -> SQ_NAN.
+template <bool METRIC>
+__device__ __forceinline__ void fwd_tile(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
+                                         int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word, float* __restrict__ partial,
+                                         unsigned* __restrict__ sq_partial, int C, int H, int W, int vec_ok) {
   __shared__ __attribute__((aligned(16))) float px[PH * PW];
   __shared__ __attribute__((aligned(16))) float py[PH * PW];
   __shared__ float rf[5][PH][TW];
@@ -186,11 +201,11 @@ __global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, con
   const int y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
   const int Ho = H - HALO, Wo = W - HALO;
   const size_t plane = (size_t)z * H * W;
-  load_patch<PH, PW>(sr + plane, px, y0, x0, H, W, vec_ok);
-  load_patch<PH, PW>(hr + plane, py, y0, x0, H, W, vec_ok);
+  load_patch<PH, PW, METRIC>(sr + plane, px, y0, x0, H, W, vec_ok);
+  load_patch<PH, PW, METRIC>(hr + plane, py, y0, x0, H, W, vec_ok);
   // the row's range class: from its partial extrema (<= NT of them), or the fixed one
   unsigned cls = (unsigned)fixed_cls;
-  if (fixed_cls < 0) {
+  if (!METRIC && fixed_cls < 0) {
     float hi = -INFINITY, lo = INFINITY;
     if ((int)threadIdx.x < ext_blocks) {
       hi = ext[((size_t)row * ext_blocks + threadIdx.x) * 2];
@@ -199,10 +214,36 @@ __global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, con
     block_extrema(hi, lo, red);
     cls = (lo < -0.5f ? 1u : 0u) | (hi > 128.f ? 2u : 0u);
   }
-  if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && z == row * C) range_word[row] = cls;
+  if (!METRIC && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && z == row * C) range_word[row] = cls;
   float C1, C2;
   ssim_constants(cls, C1, C2);
   __syncthreads();
+
+  if constexpr (METRIC) {
+    __shared__ unsigned sq_red[NW];
+    const int own_h = blockIdx.y + 1 == gridDim.y ? H - y0 : TH, own_w = blockIdx.x + 1 == gridDim.x ? W - x0 : TW;
+    unsigned acc = 0;
+    int bad = 0;
+    for (int i = threadIdx.x; i < own_h * own_w; i += NT) {
+      const int r = i / own_w, c = i - r * own_w;
+      const float d = px[r * PW + c] - py[r * PW + c];
+      if (d != d) {
+        bad = 1;
+      } else {
+        acc += (unsigned)(int)(d * d);      // integers up to 255^2: exact in fp32
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += (unsigned)__shfl_xor((int)acc, off, SAVFI_WAVE);
+    if ((threadIdx.x & (SAVFI_WAVE - 1)) == 0) sq_red[threadIdx.x / SAVFI_WAVE] = acc;
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+      unsigned tot = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) tot += sq_red[w];
+      sq_partial[((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = bad ? SQ_NAN : tot;
+    }
+  }
 
   for (int i = threadIdx.x; i < PH * TW; i += NT) {
     const int r = i / TW, c = i - r * TW;
@@ -240,6 +281,19 @@ __global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, con
   if (threadIdx.x == 0) partial[((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
+__global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
+                                               int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word,
+                                               float* __restrict__ partial, int C, int H, int W, int vec_ok) {
+  fwd_tile<false>(sr, hr, ext, ext_blocks, fixed_cls, range_word, partial, nullptr, C, H, W, vec_ok);
+}
+
+// the metric's tile kernel: unit-range pred / target in, SSIM partial sum and integer squared-error partial out
+__global__ __launch_bounds__(NT) void metric_tile(const float* __restrict__ pred, const float* __restrict__ target,
+                                                  float* __restrict__ partial, unsigned* __restrict__ sq_partial, int C, int H, int W,
+                                                  int vec_ok) {
+  fwd_tile<true>(pred, target, nullptr, 0, 2, nullptr, partial, sq_partial, C, H, W, vec_ok);
+}
+
 // result[row] = (1 - (the row's partial sums, lane-strided then a butterfly: always the same order) / n) / 2
 __global__ __launch_bounds__(64) void ssim_finish(const float* __restrict__ partial, float* __restrict__ result, int blocks, float n) {
   const float* p = partial + (size_t)blockIdx.x * blocks;
@@ -247,6 +301,37 @@ __global__ __launch_bounds__(64) void ssim_finish(const float* __restrict__ part
   for (int i = threadIdx.x; i < blocks; i += 64) acc += p[i];
   acc = wave_sum(acc);
   if (threadIdx.x == 0) result[blockIdx.x] = (1.f - acc / n) / 2.f;
+}
+
+// result[row] = {mse, ssim}: the SSIM partial sums in ssim_finish's order / n_out; the squared-error partials as 64-bit integers
+// (exact, whatever the order) -> S / (65025 n_pix) in double.  A NaN word makes the mse NaN (the SSIM sum then is NaN by itself:
+// every pixel lies in some window) and sq_sum[row] all ones.
+__global__ __launch_bounds__(64) void metric_finish(const float* __restrict__ partial, const unsigned* __restrict__ sq_partial,
+                                                    float* __restrict__ result, unsigned long long* __restrict__ sq_sum, int blocks,
+                                                    float n_out, double n_pix) {
+  const float* p = partial + (size_t)blockIdx.x * blocks;
+  const unsigned* q = sq_partial + (size_t)blockIdx.x * blocks;
+  float acc = 0.f;
+  unsigned long long S = 0;
+  int bad = 0;
+  for (int i = threadIdx.x; i < blocks; i += 64) {
+    acc += p[i];
+    const unsigned w = q[i];
+    bad |= w == SQ_NAN;
+    S += w;
+  }
+  acc = wave_sum(acc);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)S, off, SAVFI_WAVE), hi = (unsigned)__shfl_xor((int)(unsigned)(S >> 32), off, SAVFI_WAVE);
+    S += ((unsigned long long)hi << 32) | lo;
+    bad |= __shfl_xor(bad, off, SAVFI_WAVE);
+  }
+  if (threadIdx.x == 0) {
+    result[2 * blockIdx.x] = bad ? __builtin_nanf("") : (float)((double)S / (65025.0 * n_pix));
+    result[2 * blockIdx.x + 1] = acc / n_out;
+    if (sq_sum) sq_sum[blockIdx.x] = bad ? ~0ULL : S;
+  }
 }
 
 // grid (cdiv(W, BW), cdiv(H, BH), rows * C)
@@ -399,5 +484,27 @@ extern "C" int savfi_ssim_loss_bwd_f32(const float* sr, const float* hr, const f
   const float inv_2n = (float)(1.0 / (2.0 * (double)n_out));
   hipLaunchKernelGGL(ssim_bwd, dim3(savfi_cdiv(W, BW), savfi_cdiv(H, BH), rows * C), dim3(NT), 0, (hipStream_t)stream, sr, hr, g_loss,
                      range_word, g_sr, C, H, W, inv_2n, vec_ok);
+  return savfi_launch_status();
+}
+
+extern "C" int64_t savfi_psnr_ssim_scratch_bytes(int rows, int C, int H, int W) {
+  if (int e = ssim_check(rows, C, H, W)) return e;
+  // per workgroup: one float (SSIM partial sum) and one 32-bit integer (squared-error partial)
+  return (int64_t)rows * C * savfi_cdiv(W - HALO, TW) * savfi_cdiv(H - HALO, TH) * (int64_t)(sizeof(float) + sizeof(unsigned));
+}
+
+extern "C" int savfi_psnr_ssim_f32(const float* pred, const float* target, float* result, unsigned long long* sq_sum, void* scratch,
+                                   int rows, int C, int H, int W, void* stream) {
+  if (!pred || !target || !result || !scratch) return SAVFI_E_NULL;
+  if (int e = ssim_check(rows, C, H, W)) return e;
+  const int tx = savfi_cdiv(W - HALO, TW), ty = savfi_cdiv(H - HALO, TH);
+  const int vec_ok = ((((uintptr_t)pred | (uintptr_t)target) & 15u) == 0) && (W % 4 == 0);
+  float* partial = (float*)scratch;
+  unsigned* sq_partial = (unsigned*)(partial + (int64_t)rows * C * tx * ty);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(metric_tile, dim3(tx, ty, rows * C), dim3(NT), 0, st, pred, target, partial, sq_partial, C, H, W, vec_ok);
+  if (int e = savfi_launch_status()) return e;
+  hipLaunchKernelGGL(metric_finish, dim3(rows), dim3(64), 0, st, partial, sq_partial, result, sq_sum, C * tx * ty,
+                     (float)((int64_t)C * (H - HALO) * (W - HALO)), (double)C * H * W);
   return savfi_launch_status();
 }

@@ -788,6 +788,49 @@ def ssim_loss_per_sample(sr, hr):
 
 
 # --------------------------------------------------------------------------------------------
+# PSNR / SSIM evaluation metric and the frame writer          (utils.py:171-204, :276-285)
+# --------------------------------------------------------------------------------------------
+def psnr_ssim(pred01, tgt01, want_sq_sum=False):
+    """pred01, tgt01 [rows,C,H,W] in unit range -> (mse [rows], ssim [rows]) of the 0..255-quantised images, every row on its own:
+    what utils.quantize(., 1.) + ((q_p - q_t) / 255)^2 .mean() + utils.ssim(val_range=255) give per pair, in two launches for all
+    rows.  PSNR = -10 log10(mse + 1e-8).  No gradient; capturable; deterministic.  want_sq_sum: also the exact integer sums of
+    squared differences, int64 [rows] (-1 for a row that holds a NaN)."""
+    if pred01.dim() != 4 or pred01.shape != tgt01.shape or pred01.shape[2] < 11 or pred01.shape[3] < 11:
+        raise ValueError("psnr_ssim needs two [rows,C,H,W] tensors of one shape with H, W >= 11 (the window is always 11 wide), got %s, %s"
+                         % (tuple(pred01.shape), tuple(tgt01.shape)))
+    pred01, tgt01 = pred01.detach().contiguous(), tgt01.detach().contiguous()
+    _hip.require_cuda(pred01, tgt01)
+    rows, C, H, W = pred01.shape
+    res = torch.empty((rows, 2), dtype=torch.float32, device=pred01.device)
+    sq = torch.empty(rows, dtype=torch.int64, device=pred01.device) if want_sq_sum else None
+    scratch = torch.empty(_workspace_floats("savfi_psnr_ssim_scratch_bytes", rows, C, H, W), dtype=torch.uint8, device=pred01.device)
+    lib = _hip.lib()
+    _hip.launch("psnr_ssim", lambda: _hip.check(lib.savfi_psnr_ssim_f32(
+        pred01.data_ptr(), tgt01.data_ptr(), res.data_ptr(), _ptr(sq), scratch.data_ptr(), rows, C, H, W, _hip.current_stream()),
+        "savfi_psnr_ssim_f32"), nbytes=8 * pred01.numel())
+    return (res[:, 0], res[:, 1]) + ((sq,) if want_sq_sum else ())
+
+
+def frames_to_u8(x):
+    """x [N,C,H,W] (or [C,H,W], [H,W]) in unit range, C = 1 or 3 -> uint8 [N,H,W,C] ([H,W,C], [H,W]) on the device, quantised as
+    utils.save_image does (the metric's device function): a frame leaves the device as bytes."""
+    shape = x.shape
+    if x.dim() not in (2, 3, 4):
+        raise ValueError("frames_to_u8 needs [N,C,H,W], [C,H,W] or [H,W], got %s" % (tuple(shape),))
+    x4 = x.detach().reshape((1,) * (4 - x.dim()) + tuple(shape)).contiguous()
+    _hip.require_cuda(x4)
+    N, C, H, W = x4.shape
+    if C not in (1, 3):
+        raise ValueError("frames_to_u8 writes 1 or 3 channels, got %d" % C)
+    out = torch.empty((N, H, W, C), dtype=torch.uint8, device=x.device)
+    if out.numel():
+        lib = _hip.lib()
+        _hip.launch("frames_to_u8", lambda: _hip.check(lib.savfi_frames_f32_to_u8(
+            x4.data_ptr(), out.data_ptr(), N, C, H, W, _hip.current_stream()), "savfi_frames_f32_to_u8"), nbytes=5 * x4.numel())
+    return out if x.dim() == 4 else out[0] if x.dim() == 3 else out[0, :, :, 0]
+
+
+# --------------------------------------------------------------------------------------------
 # conv + bias + (leaky) ReLU with fused epilogues   (sepconv/model.py:172-194, model_utils.py:957-990)
 # --------------------------------------------------------------------------------------------
 # 3x3 / stride 1 convolutions run on savfi_conv3x3_f32 (Winograd on the fp32 matrix cores, bias + activation in its

@@ -397,6 +397,11 @@ class SceneAdaptiveInterpolation(nn.Module):
             return self.revNormalize(img)
         return img
 
+    def _eval_metrics(self, preds, targets):
+        """preds, targets [rows,C,H,W] in the network's range -> (mse [rows], ssim [rows]) device tensors of the quantised unit-range
+        images (reference utils.py:189-204 per pair): one call for all rows, no host read."""
+        return utils.psnr_ssim_rows(self._to_unit_range(preds.detach()), self._to_unit_range(targets.detach()))
+
     def _task_body(self, frames, task_id, *, num_steps, use_second_order, msl, training_phase, do_evaluation, importance):
         """Everything one task contributes to a meta-iteration (reference :366-461): adaptation, target pass(es), its
         loss term, prediction, logging scalars.  Touches no shared mutable state, so tasks can run concurrently."""
@@ -424,11 +429,8 @@ class SceneAdaptiveInterpolation(nn.Module):
         target_preds = state['preds']
         res = {'pred': self._to_unit_range(target_preds.detach().squeeze(0)).unsqueeze(0), 'logs': logs}
         if do_evaluation:
-            out01 = self._to_unit_range(target_preds.detach().squeeze(0))
-            tgt01 = self._to_unit_range(frames[self.target_idxs[1]][task_id].detach())
-            q_o, q_t = utils.quantize(out01, 1.), utils.quantize(tgt01, 1.)
-            res['mse'] = (q_o - q_t).div(255).pow(2).mean()
-            res['ssim'] = utils.ssim(q_o.unsqueeze(0), q_t.unsqueeze(0), val_range=255)
+            mse, ssim = self._eval_metrics(target_preds, frames[self.target_idxs[1]][task_id:task_id + 1])
+            res['mse'], res['ssim'] = mse[0], ssim[0]
         res['loss'] = torch.sum(torch.stack(task_losses))
         if not training_phase:
             self.net.restore_backup_stats()
@@ -549,14 +551,12 @@ class SceneAdaptiveInterpolation(nn.Module):
         per_task = torch.stack(task_terms, 0).sum(0)                            # [T]
         preds = preds.detach()
         results = []
+        if do_evaluation:          # the T tasks in one call
+            mse, ssim = self._eval_metrics(preds, frames[self.target_idxs[1]][list(ids)])
         for t, task_id in enumerate(ids):
             res = {'pred': self._to_unit_range(preds[t]).unsqueeze(0), 'logs': logs[t], 'loss': per_task[t]}
             if do_evaluation:
-                out01 = self._to_unit_range(preds[t])
-                tgt01 = self._to_unit_range(frames[self.target_idxs[1]][task_id].detach())
-                q_o, q_t = utils.quantize(out01, 1.), utils.quantize(tgt01, 1.)
-                res['mse'] = (q_o - q_t).div(255).pow(2).mean()
-                res['ssim'] = utils.ssim(q_o.unsqueeze(0), q_t.unsqueeze(0), val_range=255)
+                res['mse'], res['ssim'] = mse[t], ssim[t]
             results.append(res)
         if not training_phase:
             self.net.restore_backup_stats()
@@ -788,16 +788,15 @@ class SceneAdaptiveInterpolation(nn.Module):
             i = owner[tuple(group)]
             task_losses, preds_g, logs_g = loops[tuple(group)].run_tasks(frames, list(group), importance, accums[i])
             out = []
+            if do_evaluation:
+                mse, ssim = self._eval_metrics(torch.stack([preds_g[t] for t in range(len(group))]),
+                                               frames[self.target_idxs[1]][list(group)])
             for t, task_id in enumerate(group):
                 pred = preds_g[t]
                 res = {'loss': task_losses[t], 'pred': self._to_unit_range(pred).unsqueeze(0),
                        'logs': [(k, v) for parts in logs_g[t] for k, v in parts.items()]}
                 if do_evaluation:
-                    out01 = self._to_unit_range(pred)
-                    tgt01 = self._to_unit_range(frames[self.target_idxs[1]][task_id].detach())
-                    q_o, q_t = utils.quantize(out01, 1.), utils.quantize(tgt01, 1.)
-                    res['mse'] = (q_o - q_t).div(255).pow(2).mean()
-                    res['ssim'] = utils.ssim(q_o.unsqueeze(0), q_t.unsqueeze(0), val_range=255)
+                    res['mse'], res['ssim'] = mse[t], ssim[t]
                 out.append(res)
             return out
 

@@ -2,7 +2,7 @@
 metric), checkpoint save / load with the reference's key layout.
 
 Reference: utils.py:34-118 (checkpoints), :135-150 (AverageMeter), :171-204 (metrics);
-pytorch_msssim/__init__.py:19-75 (ssim).  Image / video writers and tensorboard are out of scope.
+pytorch_msssim/__init__.py:19-75 (ssim); :276-285 (save_image).  Video writers and tensorboard are out of scope.
 """
 import math
 import os
@@ -76,6 +76,20 @@ def calc_metrics(im_pred, im_gt, mask=None):
     return psnr, ssim(q_pred.unsqueeze(0), q_gt.unsqueeze(0), val_range=255)
 
 
+def psnr_ssim_rows(pred01, tgt01):
+    """[rows,C,H,W] x [rows,C,H,W] in [0,1] -> (mse [rows], ssim [rows]) of the quantised images, every row on its own
+    (PSNR = -10 log10(mse + 1e-8)).  Device tensors with H, W >= 11 take the fused kernel (hip_ops.psnr_ssim: two launches for all
+    rows); anything else the composition above, row by row.  The choice is made from the tensors, never from an option."""
+    pred01, tgt01 = pred01.detach(), tgt01.detach()
+    if pred01.is_cuda and tgt01.is_cuda and pred01.shape[-2] >= 11 and pred01.shape[-1] >= 11:
+        from . import hip_ops
+        return hip_ops.psnr_ssim(pred01, tgt01)
+    q_p, q_t = quantize(pred01, 1.), quantize(tgt01, 1.)
+    rows = range(pred01.shape[0])
+    return (torch.stack([(q_p[r] - q_t[r]).div(255).pow(2).mean() for r in rows]),
+            torch.stack([ssim(q_p[r:r + 1], q_t[r:r + 1], val_range=255) for r in rows]))
+
+
 # ---------------------------------------------------------------------------------------------
 # checkpoints: {'epoch', 'arch', 'state_dict', 'best_PSNR'} under checkpoint/<exp_name>/
 # ---------------------------------------------------------------------------------------------
@@ -143,11 +157,13 @@ def load_checkpoint(args, model, optimizer=None, fix_loaded=False):
 # ---------------------------------------------------------------------------------------------
 def save_image(img, path):
     from PIL import Image
-    q = quantize(img.detach().mul(255)).cpu().numpy().astype('uint8')
-    if img.dim() == 2:
-        im = Image.fromarray(q, 'L')
-    elif img.dim() == 3:
-        im = Image.fromarray(q.transpose(1, 2, 0), 'RGB')
-    else:
+    if img.dim() not in (2, 3):
         return
+    if img.is_cuda and img.dtype == torch.float32 and (img.dim() == 2 or img.shape[0] == 3):
+        from . import hip_ops
+        hwc = hip_ops.frames_to_u8(img).cpu().numpy()          # quantised on the device: bytes cross PCIe, HWC already
+        im = Image.fromarray(hwc, 'L' if img.dim() == 2 else 'RGB')
+    else:
+        q = quantize(img.detach().mul(255)).cpu().numpy().astype('uint8')
+        im = Image.fromarray(q, 'L') if img.dim() == 2 else Image.fromarray(q.transpose(1, 2, 0), 'RGB')
     im.save(path)
