@@ -162,7 +162,10 @@ __device__ __forceinline__ void ca_block_sums(float (&p)[CRM], int Cr, float (*r
     }
   __syncthreads();
   if ((int)threadIdx.x < Cr) {
-    // the association of block_sum (a butterfly over the four wave totals): bit-identical to the generic kernels
+    // the association of block_sum (a butterfly over the four wave totals).  Bit-identical to the generic kernels where the summands
+    // reach wave_sum as they are (the forward); where a caller hands over a bare product (ca_mlp_bwd_small, the parameter-gradient
+    // workgroups of ca_apply_bwd_mlp_kernel) the compiler fuses it into the first addition of the wave sum, one rounding fewer than
+    // the generic kernel's and the streaming workgroups' sums: equal to the last bit or so, not bit for bit (tests/test_small_ops_branches_gpu.py)
     static_assert(CA_T / SAVFI_WAVE == 4, "four wave totals");
     out[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][2]) + (red[threadIdx.x][1] + red[threadIdx.x][3]);
   }
@@ -329,8 +332,10 @@ __global__ __launch_bounds__(CA_T) void ca_apply_mlp_kernel(const float* __restr
 }
 
 // Backward of the same: gt = g * y + ds with ds recomputed per workgroup (ca_mlp_bwd_small's arithmetic for the workgroup's sample: the same
-// ds bit for bit), and the four parameter gradients from T workgroups of their own AT THE FRONT of the grid (task t: the whole body of
-// ca_mlp_bwd_small), which run beside the streaming workgroups instead of in a 10 us launch between the pool and the apply.
+// ds up to the rounding of the products inside its block sums, see ca_block_sums -- gt within an ulp of the separate launches', measured
+// at C = 192 and 256), and the four parameter gradients, bit for bit ca_mlp_bwd_small's, from T workgroups of their own AT THE FRONT of
+// the grid (task t: the whole body of ca_mlp_bwd_small), which run beside the streaming workgroups instead of in a 10 us launch between
+// the pool and the apply.
 __global__ __launch_bounds__(CA_T) void ca_apply_bwd_mlp_kernel(const float* __restrict__ g, const float* __restrict__ r, const float* __restrict__ s,
                                                                 const float* __restrict__ y, const float* __restrict__ a1, const float* __restrict__ w1,
                                                                 const float* __restrict__ w2, float* __restrict__ gt, float* __restrict__ gw1,

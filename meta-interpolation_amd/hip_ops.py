@@ -434,18 +434,24 @@ def _launch_mt_update(rule, lr_mode, ws, gs, lrs, ms, ss, outs, coefs, bc1, sqrt
 def mt_update(rule, lr_mode, weights, grads, lrs, m=None, s=None, bc1=None, sqrt_bc2=None,
               beta1=0.9, beta2=0.99, eps=1e-8):
     """Fused update of a list of tensors.  `lrs[i]` is a 0-dim tensor (LR_SCALAR) or a tensor shaped
-    like weights[i] (LR_ELEMENT).  m / s are updated in place by the kernel.  Returns new tensors."""
+    like weights[i] (LR_ELEMENT).  m / s are updated in place by the kernel.  Returns new tensors.
+    The kernel reads every operand as a dense array: strided weights, gradients (a transposed or expanded view) and learning-rate
+    tables are made dense here -- the learning rates differentiably; the moments cannot be copied and are refused."""
     n = len(weights)
     if n == 0:
         return []
-    _hip.require_cuda(*weights, *grads, *lrs)
-    if m is not None:
-        _hip.require_cuda(*m)
-    if s is not None:
-        _hip.require_cuda(*s)
-    spec = dict(n=n, rule=rule, lr_mode=lr_mode, grads=[g.detach() for g in grads], m=m, s=s, bc1=bc1,
+    dense = lambda ts: [t if t.is_contiguous() else t.contiguous() for t in ts]
+    ws, gs, lrs = dense(weights), dense([g.detach() for g in grads]), dense(lrs)
+    _hip.require_cuda(*ws, *gs, *lrs)
+    for name, mom in (("m", m), ("s", s)):
+        if mom is None:
+            continue
+        if any(not t.is_contiguous() for t in mom):
+            raise ValueError("mt_update: the moments `%s` are updated in place and must be contiguous (a dense copy would take the "
+                             "update with it)" % name)
+        _hip.require_cuda(*mom)
+    spec = dict(n=n, rule=rule, lr_mode=lr_mode, grads=gs, m=m, s=s, bc1=bc1,
                 sqrt_bc2=sqrt_bc2, beta1=beta1, beta2=beta2, eps=eps)
-    ws = [w if w.is_contiguous() else w.contiguous() for w in weights]
     outs = list(_MtUpdate.apply(spec, *ws, *lrs))
     filters_after_update(outs)
     return outs

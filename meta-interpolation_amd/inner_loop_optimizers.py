@@ -93,7 +93,6 @@ class _FusedInnerRule(nn.Module):
         return out, bc1, sbc2
 
     def _update_fused(self, keys, ws, gs, lrs):
-        gs = [g if g.is_contiguous() else g.contiguous() for g in gs]
         hyper = dict(beta1=self.beta1, beta2=self.beta2, eps=self.eps)
         if self.optimizer == 'SGD':
             return hip_ops.mt_update(_hip.RULE_SGD, self.lr_mode, ws, gs, lrs, **hyper)

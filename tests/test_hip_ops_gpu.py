@@ -173,7 +173,8 @@ def test_sepconv_argument_errors():
 
 
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,H,W,amp", [(1, 64, 64, 0.3), (2, 33, 47, 1.0), (1, 256, 256, 1.0), (1, 5, 3, 2.0)])
+@pytest.mark.parametrize("B,H,W,amp", [(1, 64, 64, 0.3), (2, 33, 47, 1.0), (1, 256, 256, 1.0), (1, 5, 3, 2.0),
+                                         (1, 1, 7, 1.0), (2, 6, 1, 1.0)])      # (a dimension of one: lin(n == 1), make_tap(size == 1))
 def test_voxelwarp_vs_oracle(B, H, W, amp):
     g = torch.Generator().manual_seed(H * W)
     frames = torch.rand(B, 6, H, W, generator=g) * 2 - 1
