@@ -38,6 +38,10 @@
  *   savfi_ca_pool/mlp_fwd/mlp_bwd/apply_f32   channel attention + residual of CAIN's RCAB   model_utils.py:931-953, :957-990
  *   savfi_frames_u8_to_f32     HWC uint8 frames -> normalised fp32 NCHW  data/vimeo_septuplet.py:68-80, data/video.py:44-51
  *   savfi_frames_f32_to_u8     unit-range fp32 NCHW -> quantised uint8 NHWC (what save_image writes)   utils.py:171-172, :276-285
+ *   savfi_filterinterp_fwd/bwd_f32   DAIN's adaptive warping layer (per-pixel 4x4 filter at the flow-displaced position)
+ *                                                                     dain/my_package/FilterInterpolation/filterinterpolation_cuda_kernel.cu:29-460
+ *   savfi_depthflowproj_fwd/bwd_f32  DAIN's depth-aware flow projection (scatter, average, hole fill)
+ *                                                                     dain/my_package/DepthFlowProjection/depthflowprojection_cuda_kernel.cu:29-341
  *   savfi_*_workspace_floats / savfi_bias_act_scratch_floats: sizes of the caller-owned scratch buffers (return int64_t)
  *
  * Conventions (all functions):
@@ -59,7 +63,7 @@
 extern "C" {
 #endif
 
-#define SAVFI_ABI_VERSION 23
+#define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
 #define SAVFI_E_NULL       (-1)  /* a required pointer is NULL                          */
@@ -608,6 +612,50 @@ int savfi_frames_u8_to_f32(const unsigned char* src, float* dst, int64_t N, int 
  * SAVFI_E_UNSUPPORTED otherwise.
  * ---------------------------------------------------------------------------------- */
 int savfi_frames_f32_to_u8(const float* src, unsigned char* dst, int64_t N, int C, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DAIN's adaptive warping layer (csrc/dainwarp.hip; FilterInterpolation/filterinterpolation_cuda_kernel.cu:29-460), ABI 24.
+ *   in [B,C,H,W], flow [B,2,H,W], filt [B,16,H,W], out / gout / g_in [B,C,H,W], g_flow [B,2,H,W], g_filt [B,16,H,W].
+ *   Per pixel (w_i, h_i), all in fp32: x2 = w_i + fx, y2 = h_i + fy; valid iff x2 >= 0 && y2 >= 0 && x2 <= W-1 && y2 <= H-1 &&
+ *   |fx| < W/2.f && |fy| < H/2.f (a NaN flow is invalid).  Valid: the 4 x 4 window with origin (int(x2)-1, int(y2)-1), rows and
+ *   columns clamped into the image for `in` only, tap (j,i) weighted with filt channel 4j+i; rows 0-1 "top", columns 0-1 "left";
+ *   out = (1-a)(1-b) TL + a(1-b) TR + (1-a)b BL + ab BR, a = x2 - int(x2), b = y2 - int(y2).  Invalid: out = in at that pixel.
+ *   Backward: g_in and g_filt are the adjoints of the valid branch; g_flow_x = sum_c g ((1-b)(TR-TL) + b(BR-BL)),
+ *   g_flow_y = sum_c g ((1-a)(BL-TL) + a(BR-TR)); an invalid pixel gives NO gradient to anything, `in` included (kept from
+ *   the reference).  g_in, g_flow, g_filt may each be NULL (skipped); every gradient that is written is written completely, and
+ *   the entry zeroes g_in itself (with a kernel).  Forward, g_flow and g_filt are bit-reproducible; g_in is accumulated with fp32
+ *   atomicAdd in arrival order, as in the reference, and is not.
+ *   filter_size != 4: SAVFI_E_UNSUPPORTED.  H*W <= 2^31 - 257, B, C <= 65535 and B*C*H*W < 2^40, SAVFI_E_TOOBIG otherwise.
+ * ---------------------------------------------------------------------------------- */
+int savfi_filterinterp_fwd_f32(const float* in, const float* flow, const float* filt, float* out, int B, int C, int H, int W,
+                               int filter_size, void* stream);
+int savfi_filterinterp_bwd_f32(const float* in, const float* flow, const float* filt, const float* gout, float* g_in /*nullable*/,
+                               float* g_flow /*nullable*/, float* g_filt /*nullable*/, int B, int C, int H, int W, int filter_size,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DAIN's depth-aware flow projection (csrc/dainwarp.hip; DepthFlowProjection/depthflowprojection_cuda_kernel.cu:29-341), ABI 24.
+ *   flow [B,2,H,W], w [B,1,H,W] (the depth inverse), count [B,1,H,W] and out [B,2,H,W] (both written completely).
+ *   Scatter: a source with x2, y2 inside [0,W-1] x [0,H-1] adds -w fx, -w fy and w to the targets (T,L), (T,R), (Bt,L), (Bt,R),
+ *   L = int(x2), T = int(y2), R = min(L+1, W-1), Bt = min(T+1, H-1) -- a doubled target is hit twice.  Average: out /= count where
+ *   count > 0.  fillhole != 0: a pixel with count <= 0 becomes the unweighted mean of out at the first pixel with non-zero count
+ *   to its left, right, top and bottom, over those of them with count > 0; 0 when there is none.
+ *   The sums are accumulated as 64-bit fixed-point integers (per-sample power-of-two scale from a device-side maximum, every
+ *   contribution rounded away from zero), so count, out and every decision taken from them are bit-reproducible.
+ *   `scratch`: savfi_depthflowproj_scratch_bytes(B, H, W) bytes, 8-byte aligned (SAVFI_E_UNSUPPORTED otherwise), caller-owned,
+ *   cleared by a kernel of the entry.  Five launches (four without the fill), no host read: capturable.
+ *   A source whose |w| max(|fx|, |fy|, 1) is not finite in fp32 (a NaN / Inf depth inverse, or |w| beyond ~1e29 times the flow) has
+ *   no fixed-point value: it is not scattered and does not set the scale.
+ *   Backward (a gather over the same targets; g_flow and g_w may each be NULL (skipped), one that is written is written completely;
+ *   zero at sources the validity test left out):
+ *   g_flow = -sum_t g_t w / count_t;  g_w = -sum_t sum_{x,y} g_t / count_t (f - out_t), as the reference writes it.
+ *   H*W <= 2^31 - 257, B <= 65535 and 3*B*H*W < 2^40, SAVFI_E_TOOBIG otherwise.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_depthflowproj_scratch_bytes(int B, int H, int W);
+int savfi_depthflowproj_fwd_f32(const float* flow, const float* w, float* count, float* out, void* scratch, int B, int H, int W,
+                                int fillhole, void* stream);
+int savfi_depthflowproj_bwd_f32(const float* flow, const float* w, const float* count, const float* out, const float* gout,
+                                float* g_flow /*nullable*/, float* g_w /*nullable*/, int B, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ RULE_SGD, RULE_ADAM, RULE_ADAMAX_LSLR, RULE_ADAMAX_MSGD = 0, 1, 2, 3
 LR_SCALAR, LR_ELEMENT = 0, 1
 SSIM_RANGE_PER_ROW, SSIM_RANGE_BATCH, SSIM_RANGE_FIXED = 0, 1, 2
 SEPCONV_PARTITION_WS, SEPCONV_PARTITION_X6, SEPCONV_PARTITION_FP32 = 0, 1, 2
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _ERRORS = {-1: "SAVFI_E_NULL (a required pointer is NULL)",
            -2: "SAVFI_E_SHAPE (bad or inconsistent dimension)",
@@ -135,6 +135,11 @@ _PROTOTYPES = {
     "savfi_bias_act_fwd_f32": [_P, _P, c_int, c_int, c_int, c_float, _P],
     "savfi_bias_act_scratch_floats": [c_int, c_int, c_int],
     "savfi_bias_act_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P],
+    "savfi_filterinterp_fwd_f32": [_P, _P, _P, _P] + [c_int] * 5 + [_P],
+    "savfi_filterinterp_bwd_f32": [_P] * 7 + [c_int] * 5 + [_P],
+    "savfi_depthflowproj_scratch_bytes": [c_int, c_int, c_int],
+    "savfi_depthflowproj_fwd_f32": [_P] * 5 + [c_int] * 4 + [_P],
+    "savfi_depthflowproj_bwd_f32": [_P] * 7 + [c_int] * 3 + [_P],
 }
 
 _lib = None

@@ -837,6 +837,110 @@ def frames_to_u8(x):
 
 
 # --------------------------------------------------------------------------------------------
+# DAIN's adaptive warping layer and depth-aware flow projection
+#   (dain/my_package/FilterInterpolation/FilterInterpolationLayer.py, dain/my_package/DepthFlowProjection/DepthFlowProjectionLayer.py)
+# --------------------------------------------------------------------------------------------
+def filterinterp_bytes(B, C, H, W, grads=0):
+    """Algorithmic HBM bytes of one adaptive-warping call (each operand once): forward in + flow + filt + out; backward (grads=1)
+    in + flow + filt + gout and the three gradients (g_in is written twice: cleared, then accumulated)."""
+    px = B * H * W
+    return 4 * px * ((2 * C + 18) if not grads else (2 * C + 18 + 2 * C + 18))
+
+
+def depthflowproj_bytes(B, H, W, grads=0):
+    """Algorithmic HBM bytes of one flow-projection call: forward flow + w read twice (maximum pass, scatter), three 64-bit
+    accumulators cleared and read, count + out written; backward flow + w + count + out + gout read, g_flow + g_w written."""
+    px = B * H * W
+    return px * ((2 * 12 + 2 * 24 + 12) if not grads else 4 * 11)
+
+
+class _FilterInterpolation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input1, input2, input3):
+        _hip.require_cuda(input1, input2, input3)
+        B, C, H, W = input1.shape
+        if input2.shape != (B, 2, H, W) or input3.shape != (B, 16, H, W):
+            raise ValueError("filter_interpolation needs input [B,C,H,W], flow [B,2,H,W] and a 4 x 4 filter [B,16,H,W], got %s, %s, %s"
+                             % (tuple(input1.shape), tuple(input2.shape), tuple(input3.shape)))
+        out = torch.empty_like(input1)
+        lib = _hip.lib()
+        _hip.launch("filterinterp_fwd", lambda: _hip.check(lib.savfi_filterinterp_fwd_f32(
+            input1.data_ptr(), input2.data_ptr(), input3.data_ptr(), out.data_ptr(), B, C, H, W, 4, _hip.current_stream()),
+            "savfi_filterinterp_fwd_f32"), nbytes=filterinterp_bytes(B, C, H, W))
+        ctx.save_for_backward(input1, input2, input3)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradoutput):
+        input1, input2, input3 = ctx.saved_tensors
+        B, C, H, W = input1.shape
+        gradoutput = gradoutput.contiguous()
+        need = ctx.needs_input_grad
+        # every gradient the entry writes is written completely (g_in is cleared by the entry itself)
+        g1 = torch.empty_like(input1) if need[0] else None
+        g2 = torch.empty_like(input2) if need[1] else None
+        g3 = torch.empty_like(input3) if need[2] else None
+        lib = _hip.lib()
+        _hip.launch("filterinterp_bwd", lambda: _hip.check(lib.savfi_filterinterp_bwd_f32(
+            input1.data_ptr(), input2.data_ptr(), input3.data_ptr(), gradoutput.data_ptr(), _ptr(g1), _ptr(g2), _ptr(g3), B, C, H, W, 4,
+            _hip.current_stream()), "savfi_filterinterp_bwd_f32"), nbytes=filterinterp_bytes(B, C, H, W, grads=1))
+        return g1, g2, g3
+
+
+def filter_interpolation(input, flow, filt):
+    """DAIN's adaptive warping layer (FilterInterpolationLayer.apply): input [B,C,H,W], flow [B,2,H,W], filt [B,16,H,W] -> [B,C,H,W].
+    First order only (the backward is once_differentiable: a second derivative raises).  g_input is accumulated with fp32 atomics
+    and is the one result that is not bit-reproducible; everything else is."""
+    return _FilterInterpolation.apply(input.contiguous(), flow.contiguous(), filt.contiguous())
+
+
+class _DepthFlowProjection(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input1, input2, fillhole):
+        _hip.require_cuda(input1, input2)
+        B, two, H, W = input1.shape
+        if two != 2 or input2.shape != (B, 1, H, W):
+            raise ValueError("depth_flow_projection needs flow [B,2,H,W] and a depth inverse [B,1,H,W], got %s, %s"
+                             % (tuple(input1.shape), tuple(input2.shape)))
+        count = torch.empty((B, 1, H, W), dtype=input1.dtype, device=input1.device)
+        output = torch.empty_like(input1)
+        scratch = torch.empty(_workspace_floats("savfi_depthflowproj_scratch_bytes", B, H, W), dtype=torch.uint8, device=input1.device)
+        lib = _hip.lib()
+        _hip.launch("depthflowproj_fwd", lambda: _hip.check(lib.savfi_depthflowproj_fwd_f32(
+            input1.data_ptr(), input2.data_ptr(), count.data_ptr(), output.data_ptr(), scratch.data_ptr(), B, H, W, int(bool(fillhole)),
+            _hip.current_stream()), "savfi_depthflowproj_fwd_f32"), nbytes=depthflowproj_bytes(B, H, W))
+        # as the reference saves them (DepthFlowProjectionLayer.py:47): the output AFTER the hole fill
+        ctx.save_for_backward(input1, input2, count, output)
+        ctx.mark_non_differentiable(count)
+        return output, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradoutput, _gcount):
+        input1, input2, count, output = ctx.saved_tensors
+        B, _, H, W = input1.shape
+        gradoutput = gradoutput.contiguous()
+        need = ctx.needs_input_grad
+        g1 = torch.empty_like(input1) if need[0] else None       # a gradient that is not needed goes to the C ABI as NULL
+        g2 = torch.empty_like(input2) if need[1] else None
+        lib = _hip.lib()
+        _hip.launch("depthflowproj_bwd", lambda: _hip.check(lib.savfi_depthflowproj_bwd_f32(
+            input1.data_ptr(), input2.data_ptr(), count.data_ptr(), output.data_ptr(), gradoutput.data_ptr(), _ptr(g1), _ptr(g2),
+            B, H, W, _hip.current_stream()), "savfi_depthflowproj_bwd_f32"), nbytes=depthflowproj_bytes(B, H, W, grads=1))
+        return g1, g2, None
+
+
+def depth_flow_projection(flow, depth_inv, fillhole, return_count=False):
+    """DAIN's depth-aware flow projection (DepthFlowProjectionLayer.apply): flow [B,2,H,W], depth_inv [B,1,H,W] -> projected flow
+    [B,2,H,W]; fillhole: fill pixels nothing landed on from their nearest valid neighbours in four directions (the reference sets
+    it when the flow needs no gradient).  Bit-reproducible, forward and backward.  return_count: also the accumulated depth
+    inverses [B,1,H,W] (no gradient)."""
+    out, count = _DepthFlowProjection.apply(flow.contiguous(), depth_inv.contiguous(), fillhole)
+    return (out, count) if return_count else out
+
+
+# --------------------------------------------------------------------------------------------
 # conv + bias + (leaky) ReLU with fused epilogues   (sepconv/model.py:172-194, model_utils.py:957-990)
 # --------------------------------------------------------------------------------------------
 # 3x3 / stride 1 convolutions run on savfi_conv3x3_f32 (Winograd on the fp32 matrix cores, bias + activation in its

@@ -166,6 +166,9 @@ class SceneAdaptiveInterpolation(nn.Module):
             self.net = net.to(self.device)
         else:
             if args.model not in MODEL_REGISTRY:
+                if args.model == 'dain':
+                    raise NotImplementedError("Model not implemented yet! DAIN's two own ops exist (dain/my_package: "
+                                              "FilterInterpolationModule, DepthFlowProjectionModule); the MetaDAIN plugin does not yet.")
                 raise NotImplementedError('Model not implemented yet!')
             print('Building %s model...' % args.model)
             self.net = MODEL_REGISTRY[args.model](args, not args.resume).to(self.device)
