@@ -42,6 +42,10 @@
  *                                                                     dain/my_package/FilterInterpolation/filterinterpolation_cuda_kernel.cu:29-460
  *   savfi_depthflowproj_fwd/bwd_f32  DAIN's depth-aware flow projection (scatter, average, hole fill)
  *                                                                     dain/my_package/DepthFlowProjection/depthflowprojection_cuda_kernel.cu:29-341
+ *   savfi_correlation_fwd/bwd_f32    PWC-Net's cost-volume correlation (md = 4), LeakyReLU fused   dain/PWCNet/correlation_package_pytorch1_0/
+ *                                                                     correlation_cuda_kernel.cu:73-340
+ *   savfi_pwcwarp_fwd_f32            PWC-Net's warp: bilinear sample (align_corners) times the thresholded sample of ones
+ *                                                                     dain/PWCNet/PWCNet.py:158-198
  *   savfi_*_workspace_floats / savfi_bias_act_scratch_floats: sizes of the caller-owned scratch buffers (return int64_t)
  *
  * Conventions (all functions):
@@ -63,6 +67,9 @@
 extern "C" {
 #endif
 
+/* Counts INCOMPATIBLE changes: an entry removed or its arguments or meaning changed.  Entries that are only added leave it alone
+ * (a binding written for the older header still works).  Added under 24: savfi_correlation_fwd_f32, savfi_correlation_bwd_f32,
+ * savfi_pwcwarp_fwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -656,6 +663,38 @@ int savfi_depthflowproj_fwd_f32(const float* flow, const float* w, float* count,
                                 int fillhole, void* stream);
 int savfi_depthflowproj_bwd_f32(const float* flow, const float* w, const float* count, const float* out, const float* gout,
                                 float* g_flow /*nullable*/, float* g_w /*nullable*/, int B, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * PWC-Net's correlation (csrc/correlation.hip; correlation_package_pytorch1_0/correlation_cuda_kernel.cu), added under ABI 24.
+ *   f1, f2, g1, g2 [N,C,H,W]; out, gout [N,(2md+1)^2,H,W].  The reference's pad_size = max_displacement = md, kernel_size = 1,
+ *   stride1 = stride2 = 1, corr_multiply = 1; md = 4 only (SAVFI_E_UNSUPPORTED otherwise).  p = the input with md zeros around it:
+ *     out[n,tc,y,x] = (1/C) sum_c p1[n,c,y,x] p2[n,c,y+tj,x+ti],  tj, ti in -md..md,  tc = (tj+md)(2md+1) + (ti+md),
+ *   channels summed in order in fp32, divided by C, then out = out > 0 ? out : slope * out (slope = 1: no activation).  A
+ *   displacement that leaves the frame is multiplied by the padded zero, not skipped: a NaN / inf of f1 gives NaN in all 81 channels.
+ *   NCHW is read in place (no padded channels-last copies).  Every output element is written; no memset, no atomics.
+ *   Backward: ge = gout * (out > 0 ? 1 : slope) when `out` (the forward's result, run with the same slope) is given, gout otherwise;
+ *     g1[n,c,y,x] = (1/C) sum_tc ge[n,tc,y,x] p2[n,c,y+tj,x+ti]             (never skipped: padded zeros)
+ *     g2[n,c,y,x] = (1/C) sum_tc ge[n,tc,y-tj,x-ti] f1[n,c,y-tj,x-ti]       (over the tc whose source pixel is inside the frame)
+ *   both as gathers with sequential fp32 sums over tc.  g1 or g2 may be NULL (skipped; with both NULL nothing is launched).
+ *   Forward and backward are bit-reproducible and capturable.
+ *   H*W <= 2^31 - 257, H <= 4 * 65535, N, C <= 65535, N * ceil(C/16) <= 65535 and N * max(C, 81) * H*W < 2^40, SAVFI_E_TOOBIG otherwise.
+ * ---------------------------------------------------------------------------------- */
+int savfi_correlation_fwd_f32(const float* f1, const float* f2, float* out, int N, int C, int H, int W, int md, float slope,
+                              void* stream);
+int savfi_correlation_bwd_f32(const float* f1, const float* f2, const float* gout, const float* out /*nullable*/, float slope,
+                              float* g1 /*nullable*/, float* g2 /*nullable*/, int N, int C, int H, int W, int md, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * PWC-Net's warp (csrc/correlation.hip; dain/PWCNet/PWCNet.py:158-198), added under ABI 24.  Forward only.
+ *   img, out [N,C,H,W], flow [N,2,H,W] in pixels, `scale` the level's flow scale (the reference's `up_flow * 0.625` etc.).
+ *   out = bilinear(img, ix, iy) * (mask >= 0.9999f ? 1 : 0), mask = the same bilinear sample of an all-ones image, with, each step one
+ *   fp32 operation:  vx = x + flow_x * scale;  nx = 2 vx / max(W-1, 1) - 1;  ix = ((nx + 1) / 2) (W - 1)   (grid_sample with
+ *   align_corners=True, as the torch the reference pins runs it), likewise in y;  x0 = floor(ix);  weights nw = (x0+1-ix)(y0+1-iy),
+ *   ne = (ix-x0)(y0+1-iy), sw = (x0+1-ix)(iy-y0), se = (ix-x0)(iy-y0);  image and mask sums in the order nw, ne, sw, se over the
+ *   corners inside the frame (one outside is skipped).  A NaN / inf position samples nothing: mask = 0, out = 0.
+ *   H*W <= 2^31 - 257, N, C <= 65535, N * ceil(C/8) <= 65535 and N*C*H*W < 2^40, SAVFI_E_TOOBIG otherwise.
+ * ---------------------------------------------------------------------------------- */
+int savfi_pwcwarp_fwd_f32(const float* img, const float* flow, float scale, float* out, int N, int C, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

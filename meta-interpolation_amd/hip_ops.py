@@ -941,6 +941,80 @@ def depth_flow_projection(flow, depth_inv, fillhole, return_count=False):
 
 
 # --------------------------------------------------------------------------------------------
+# PWC-Net's cost-volume correlation and warp     (dain/PWCNet/correlation_package_pytorch1_0/correlation.py, dain/PWCNet/PWCNet.py:158-198)
+# --------------------------------------------------------------------------------------------
+def correlation_bytes(N, C, H, W, md=4, grads=0):
+    """Algorithmic HBM bytes of one correlation call (each operand once): forward f1 + f2 + out; backward (grads=1) f1 + f2 + gout + out
+    and both gradients."""
+    px, nt = N * H * W, (2 * md + 1) ** 2
+    return 4 * px * ((2 * C + nt) if not grads else (4 * C + 2 * nt))
+
+
+def pwc_warp_bytes(N, C, H, W):
+    """Algorithmic HBM bytes of one PWC warp: img + flow + out."""
+    return 4 * N * H * W * (2 * C + 2)
+
+
+class _Correlation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f1, f2, md, slope):
+        _hip.require_cuda(f1, f2)
+        N, C, H, W = f1.shape
+        if f2.shape != f1.shape:
+            raise ValueError("correlation needs two feature maps of one shape [N,C,H,W], got %s, %s" % (tuple(f1.shape), tuple(f2.shape)))
+        out = torch.empty((N, (2 * md + 1) ** 2, H, W), dtype=f1.dtype, device=f1.device)       # written completely by the kernel
+        lib = _hip.lib()
+        _hip.launch("correlation_fwd", lambda: _hip.check(lib.savfi_correlation_fwd_f32(
+            f1.data_ptr(), f2.data_ptr(), out.data_ptr(), N, C, H, W, md, slope, _hip.current_stream()),
+            "savfi_correlation_fwd_f32"), nbytes=correlation_bytes(N, C, H, W, md))
+        ctx.md, ctx.slope = md, slope
+        ctx.save_for_backward(f1, f2, out if slope != 1.0 else None)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        f1, f2, out = ctx.saved_tensors
+        N, C, H, W = f1.shape
+        gout = gout.contiguous()
+        need = ctx.needs_input_grad
+        g1 = torch.empty_like(f1) if need[0] else None          # a gradient that is not needed goes to the C ABI as NULL
+        g2 = torch.empty_like(f2) if need[1] else None
+        lib = _hip.lib()
+        _hip.launch("correlation_bwd", lambda: _hip.check(lib.savfi_correlation_bwd_f32(
+            f1.data_ptr(), f2.data_ptr(), gout.data_ptr(), _ptr(out), ctx.slope, _ptr(g1), _ptr(g2), N, C, H, W, ctx.md,
+            _hip.current_stream()), "savfi_correlation_bwd_f32"), nbytes=correlation_bytes(N, C, H, W, ctx.md, grads=1))
+        return g1, g2, None, None
+
+
+def correlation(f1, f2, md=4, slope=1.0):
+    """PWC-Net's cost volume: out[n, (tj+md)(2md+1) + ti+md, y, x] = mean_c f1[n,c,y,x] f2[n,c,y+tj,x+ti] over zero-padded maps, then
+    LeakyReLU(slope) in the same kernel (slope = 1: none).  [N,C,H,W] x 2 -> [N,(2md+1)^2,H,W]; md = 4 is the one the library builds.
+    First order only (once_differentiable); forward and both gradients are bit-reproducible."""
+    return _Correlation.apply(f1.contiguous(), f2.contiguous(), int(md), float(slope))
+
+
+def pwc_warp(img, flow, scale=1.0):
+    """PWCDCNet.warp(img, flow * scale): img [N,C,H,W] sampled bilinearly at (x + scale u, y + scale v) with zeros outside -- grid_sample
+    with align_corners=True, as the torch the reference pins for DAIN ran it -- and zeroed where the same sample of an all-ones image is
+    below 0.9999.  One launch; forward only, as the frozen flow estimator needs it."""
+    img, flow = img.contiguous(), flow.contiguous()
+    _hip.require_cuda(img, flow)
+    if torch.is_grad_enabled() and (img.requires_grad or flow.requires_grad):
+        raise NotImplementedError("pwc_warp has no backward: PWC-Net is frozen on every path of the reference's system "
+                                  "(meta_learning_system.py:96-101); call it under torch.no_grad()")
+    N, C, H, W = img.shape
+    if flow.shape != (N, 2, H, W):
+        raise ValueError("pwc_warp needs img [N,C,H,W] and flow [N,2,H,W], got %s, %s" % (tuple(img.shape), tuple(flow.shape)))
+    out = torch.empty_like(img)
+    lib = _hip.lib()
+    _hip.launch("pwcwarp_fwd", lambda: _hip.check(lib.savfi_pwcwarp_fwd_f32(
+        img.data_ptr(), flow.data_ptr(), float(scale), out.data_ptr(), N, C, H, W, _hip.current_stream()),
+        "savfi_pwcwarp_fwd_f32"), nbytes=pwc_warp_bytes(N, C, H, W))
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # conv + bias + (leaky) ReLU with fused epilogues   (sepconv/model.py:172-194, model_utils.py:957-990)
 # --------------------------------------------------------------------------------------------
 # 3x3 / stride 1 convolutions run on savfi_conv3x3_f32 (Winograd on the fp32 matrix cores, bias + activation in its

@@ -168,7 +168,8 @@ class SceneAdaptiveInterpolation(nn.Module):
             if args.model not in MODEL_REGISTRY:
                 if args.model == 'dain':
                     raise NotImplementedError("Model not implemented yet! DAIN's two own ops exist (dain/my_package: "
-                                              "FilterInterpolationModule, DepthFlowProjectionModule); the MetaDAIN plugin does not yet.")
+                                              "FilterInterpolationModule, DepthFlowProjectionModule) and so does its flow estimator "
+                                              "(dain/PWCNet: PWCDCNet, Correlation); the MetaDAIN plugin does not yet.")
                 raise NotImplementedError('Model not implemented yet!')
             print('Building %s model...' % args.model)
             self.net = MODEL_REGISTRY[args.model](args, not args.resume).to(self.device)
