@@ -46,6 +46,11 @@
  *                                                                     correlation_cuda_kernel.cu:73-340
  *   savfi_pwcwarp_fwd_f32            PWC-Net's warp: bilinear sample (align_corners) times the thresholded sample of ones
  *                                                                     dain/PWCNet/PWCNet.py:158-198
+ *   savfi_bn_stats/bn_apply_relu/bn_running_update_f32   train-mode BatchNorm2d + ReLU of DAIN's depth hourglass, per task
+ *                                                                     dain/MegaDepth/pytorch_DIW_scratch.py:31-760
+ *   savfi_maxpool2x2/upnearest2x_add/add_relu_f32        the pooling, upsample + skip sum and residual tail of DAIN's sub-networks
+ *                                                                     dain/networks/DAIN.py:692-824, dain/Resblock/BasicBlock.py:97-149
+ *   savfi_charbonnier_f32 / _bwd_f32 DAIN's Charbonnier loss         dain/loss_function.py:14-16
  *   savfi_*_workspace_floats / savfi_bias_act_scratch_floats: sizes of the caller-owned scratch buffers (return int64_t)
  *
  * Conventions (all functions):
@@ -69,7 +74,9 @@ extern "C" {
 
 /* Counts INCOMPATIBLE changes: an entry removed or its arguments or meaning changed.  Entries that are only added leave it alone
  * (a binding written for the older header still works).  Added under 24: savfi_correlation_fwd_f32, savfi_correlation_bwd_f32,
- * savfi_pwcwarp_fwd_f32. */
+ * savfi_pwcwarp_fwd_f32; then, for DAIN's frozen front and rectify net, savfi_bn_stats_scratch_floats, savfi_bn_stats_f32,
+ * savfi_bn_apply_relu_f32, savfi_bn_running_update_f32, savfi_maxpool2x2_f32, savfi_upnearest2x_add_f32, savfi_add_relu_f32,
+ * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -695,6 +702,50 @@ int savfi_correlation_bwd_f32(const float* f1, const float* f2, const float* gou
  *   H*W <= 2^31 - 257, N, C <= 65535, N * ceil(C/8) <= 65535 and N*C*H*W < 2^40, SAVFI_E_TOOBIG otherwise.
  * ---------------------------------------------------------------------------------- */
 int savfi_pwcwarp_fwd_f32(const float* img, const float* flow, float scale, float* out, int N, int C, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DAIN's frozen front and rectify net (csrc/dainnet.hip, csrc/loss.hip), added under ABI 24.  Forward only unless said otherwise;
+ * float32 NCHW read in place; no memset, no atomics; bit-reproducible and capturable.  Every entry validates before it launches:
+ * NULL, then SHAPE, then UNSUPPORTED, then TOOBIG.
+ *
+ * Train-mode BatchNorm2d + ReLU.  x [N,C,H,W]; a GROUP is n_per_group consecutive samples (N % n_per_group == 0) and has statistics
+ * of its own: mean[g * stat_stride + c], var[g * stat_stride + c] (biased variance) over its n_per_group * H * W values, which must
+ * be at least 2 (SAVFI_E_SHAPE for a count of 1, as torch raises).  Two passes (mean, then centred squares) in a summation order that
+ * depends on (n_per_group, H, W) alone: a group's statistics are the same bits whatever else the batch holds and wherever the tensor
+ * lies.  scratch: savfi_bn_stats_scratch_floats floats (0: none needed, scratch may be NULL).
+ *   savfi_bn_apply_relu_f32: out[n, c_off + c] = relu((x[n,c] - mean) / sqrt(var + eps) * gamma[c] + beta[c]) into an output of
+ *   C_total >= c_off + C channels (the other channels are not touched); gamma / beta may be NULL (1 / 0); statistics of group
+ *   n / n_per_group.  Eval mode: the running buffers with n_per_group = N and stat_stride = 0.
+ *   savfi_bn_running_update_f32: running[i][:] = (1 - momentum) running[i][:] + momentum * (stat[i][:] * unbias[i]) for n buffers of
+ *   numel[i] floats (host arrays of device pointers / sizes / factors; unbias NULL = 1), ceil(n / SAVFI_MT_MAX_TENSORS) launches.
+ * N, C <= 65535, H*W <= 2^31 - 1025, N * C_total * H*W < 2^40, SAVFI_E_TOOBIG otherwise.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_bn_stats_scratch_floats(int N, int C, int H, int W, int n_per_group);
+int savfi_bn_stats_f32(const float* x, float* mean, float* var, int64_t stat_stride, float* scratch /*nullable*/, int N, int C, int H, int W,
+                       int n_per_group, void* stream);
+int savfi_bn_apply_relu_f32(const float* x, const float* mean, const float* var, int64_t stat_stride, const float* gamma /*nullable*/,
+                            const float* beta /*nullable*/, float eps, float* out, int N, int C, int H, int W, int n_per_group, int c_off,
+                            int C_total, void* stream);
+int savfi_bn_running_update_f32(int n, float* const* running, const float* const* stat, const int64_t* numel, const float* unbias,
+                                float momentum, void* stream);
+
+/* nn.MaxPool2d(2, 2) of `planes` planes [H,W] -> [H/2, W/2] (odd sides floor; H, W >= 2); ATen's scan (rows, then columns, a NaN
+ * replaces the running maximum), so NaN propagates with ATen's bits.  planes <= 65535. */
+int savfi_maxpool2x2_f32(const float* in, float* out, int64_t planes, int H, int W, void* stream);
+
+/* out = skip + UpsamplingNearest2d(2)(low): low [planes,h,w], skip / out [planes,H,W] with H == 2h and W == 2w exactly
+ * (SAVFI_E_SHAPE otherwise).  planes <= 65535. */
+int savfi_upnearest2x_add_f32(const float* low, const float* skip, float* out, int64_t planes, int h, int w, int H, int W, void* stream);
+
+/* y = relu(a + r) over n floats (NaN kept).  Its derivative is savfi_bias_act_bwd_f32 on y, for both inputs. */
+int savfi_add_relu_f32(const float* a, const float* r, float* y, int64_t n, void* stream);
+
+/* Charbonnier loss: result[row] = mean_i sqrt((a - b)^2 + eps^2) for `rows` rows of n floats, on the row reduction of
+ * savfi_l1_mse_f32 (scratch: savfi_l1_mse_scratch_floats(rows, n)); eps > 0.  Backward: g_a = g_loss[row] / n * d / sqrt(d^2 + eps^2),
+ * exactly 0 where d == 0 (g_b = -g_a). */
+int savfi_charbonnier_f32(const float* a, const float* b, float* result, float* scratch, int rows, int64_t n, float eps, void* stream);
+int savfi_charbonnier_bwd_f32(const float* a, const float* b, const float* g_loss, float* g_a, int rows, int64_t n, float eps,
+                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,15 @@ _PROTOTYPES = {
     "savfi_correlation_fwd_f32": [_P, _P, _P] + [c_int] * 5 + [c_float, _P],
     "savfi_correlation_bwd_f32": [_P, _P, _P, _P, c_float, _P, _P] + [c_int] * 5 + [_P],
     "savfi_pwcwarp_fwd_f32": [_P, _P, c_float, _P] + [c_int] * 4 + [_P],
+    "savfi_bn_stats_scratch_floats": [c_int] * 5,
+    "savfi_bn_stats_f32": [_P, _P, _P, c_int64, _P] + [c_int] * 5 + [_P],
+    "savfi_bn_apply_relu_f32": [_P, _P, _P, c_int64, _P, _P, c_float, _P] + [c_int] * 7 + [_P],
+    "savfi_bn_running_update_f32": [c_int, _PP, _PP, _I64P, _FP, c_float, _P],
+    "savfi_maxpool2x2_f32": [_P, _P, c_int64, c_int, c_int, _P],
+    "savfi_upnearest2x_add_f32": [_P, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P],
+    "savfi_add_relu_f32": [_P, _P, _P, c_int64, _P],
+    "savfi_charbonnier_f32": [_P, _P, _P, _P, c_int, c_int64, c_float, _P],
+    "savfi_charbonnier_bwd_f32": [_P, _P, _P, _P, c_int, c_int64, c_float, _P],
 }
 
 _lib = None

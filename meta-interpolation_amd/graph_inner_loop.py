@@ -45,6 +45,8 @@ def supported(system, use_second_order):
     a = system.args
     if a.attenuate and (system._routing_known_incomplete() or not GRAPH_L2F):
         return False
+    if not getattr(system.net, 'graph_capture', True):      # a plugin that has not opted in (dain): the sequential eager task body
+        return False
     return (bool(getattr(a, 'graph_inner_loop', 0)) and system.device.type == 'cuda' and not use_second_order
             and hasattr(system.inner_loop_optimizer, 'lr_mode'))
 

@@ -1015,6 +1015,210 @@ def pwc_warp(img, flow, scale=1.0):
 
 
 # --------------------------------------------------------------------------------------------
+# DAIN's frozen front and rectify net: BatchNorm per task, max-pool, nearest x2 + add, add + ReLU, Charbonnier   (csrc/dainnet.hip)
+# --------------------------------------------------------------------------------------------
+CHARBONNIER_EPS = 1e-8          # dain/networks/DAIN.py:638
+
+
+def _frozen(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError("%s has no backward: DAIN's front is frozen on every path of the reference's system "
+                                  "(meta_learning_system.py:96-101); call it under torch.no_grad()" % what)
+
+
+def _stat_view(t, C, what):
+    """A [G, C] view of per-group statistics whose channels are adjacent (a column slice of a flat [G, total] buffer) -> (G, stride)."""
+    if not t.is_cuda:
+        raise NotImplementedError("savfi HIP ops need device tensors (%s)" % what)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != C or (C > 1 and t.stride(1) != 1):
+        raise ValueError("%s must be a float32 [groups, %d] view with adjacent channels, got %s %s stride %s"
+                         % (what, C, t.dtype, tuple(t.shape), t.stride()))
+    return t.shape[0], (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def bn_stats(x, n_per_group, mean=None, var=None):
+    """Per (group, channel) mean and biased variance of x [N,C,H,W] over the n_per_group * H * W values of each group of n_per_group
+    consecutive samples: what train-mode BatchNorm2d normalises with when a group is a call of its own.  A group's results do not depend,
+    bit for bit, on what else is in the batch.  mean / var: [N / n_per_group, C] views to write into (column slices of a flat buffer
+    are fine), allocated when None.  Returns (mean, var).  Forward only."""
+    x = x.contiguous()
+    _hip.require_cuda(x)
+    _frozen("bn_stats", x)
+    N, C, H, W = x.shape
+    n_per_group = int(n_per_group)
+    if n_per_group <= 0 or N % n_per_group:
+        raise ValueError("a batch of %d samples is no multiple of n_per_group = %d" % (N, n_per_group))
+    if n_per_group * H * W == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(x.shape),))
+    G = N // n_per_group
+    if mean is None:
+        mean, var = x.new_empty(G, C), x.new_empty(G, C)
+    (gm, sm), (gv, sv) = _stat_view(mean, C, "mean"), _stat_view(var, C, "var")
+    if gm != G or gv != G or sm != sv:
+        raise ValueError("mean and var must be [%d, %d] views with one group stride" % (G, C))
+    nscratch = _workspace_floats("savfi_bn_stats_scratch_floats", N, C, H, W, n_per_group)
+    scratch = x.new_empty(nscratch) if nscratch else None
+    lib = _hip.lib()
+    _hip.launch("bn_stats", lambda: _hip.check(lib.savfi_bn_stats_f32(
+        x.data_ptr(), mean.data_ptr(), var.data_ptr(), sm, None if scratch is None else scratch.data_ptr(), N, C, H, W, n_per_group,
+        _hip.current_stream()), "savfi_bn_stats_f32"), nbytes=8 * x.numel())
+    return mean, var
+
+
+def bn_apply_relu(x, mean, var, n_per_group, gamma=None, beta=None, eps=1e-5, out=None, c_off=0):
+    """relu((x - mean) / sqrt(var + eps) * gamma + beta) with the statistics of each sample's group (mean / var: [groups, C] views, see
+    bn_stats; eval mode: the running buffers as [1, C] with n_per_group = N), written into channels [c_off, c_off + C) of `out`
+    [N, C_total, H, W] (allocated with C_total = C when None): the branches of an inception block land in their concatenation.
+    Forward only."""
+    x = x.contiguous()
+    _hip.require_cuda(x, gamma, beta, out)
+    _frozen("bn_apply_relu", x, gamma, beta)
+    N, C, H, W = x.shape
+    n_per_group = int(n_per_group)
+    if n_per_group <= 0 or N % n_per_group:
+        raise ValueError("a batch of %d samples is no multiple of n_per_group = %d" % (N, n_per_group))
+    (gm, sm), (gv, sv) = _stat_view(mean, C, "mean"), _stat_view(var, C, "var")
+    if gm != N // n_per_group or gv != gm or sm != sv:
+        raise ValueError("mean and var must be [%d, %d] views with one group stride" % (N // n_per_group, C))
+    if out is None:
+        out = x.new_empty(N, C, H, W)
+    if out.dim() != 4 or out.shape[0] != N or tuple(out.shape[2:]) != (H, W) or c_off < 0 or c_off + C > out.shape[1]:
+        raise ValueError("out %s cannot take channels [%d, %d) of %s" % (tuple(out.shape), c_off, c_off + C, tuple(x.shape)))
+    lib = _hip.lib()
+    _hip.launch("bn_apply_relu", lambda: _hip.check(lib.savfi_bn_apply_relu_f32(
+        x.data_ptr(), mean.data_ptr(), var.data_ptr(), sm, None if gamma is None else gamma.data_ptr(),
+        None if beta is None else beta.data_ptr(), float(eps), out.data_ptr(), N, C, H, W, n_per_group, int(c_off), out.shape[1],
+        _hip.current_stream()), "savfi_bn_apply_relu_f32"), nbytes=8 * x.numel())
+    return out
+
+
+def bn_running_update(running, stats, unbias, momentum=0.1):
+    """running[i] <- (1 - momentum) running[i] + momentum * (stats[i] * unbias[i]) for lists of float32 device vectors (the running
+    means and variances of every BatchNorm of a network, the statistics of one forward): ceil(n / 48) launches."""
+    running, stats = list(running), list(stats)
+    if not running:
+        return
+    for r, s in zip(running, stats):
+        if not (r.is_cuda and s.is_cuda):
+            raise NotImplementedError("savfi HIP ops need device tensors (bn_running_update)")
+        assert r.dtype == s.dtype == torch.float32 and r.is_contiguous() and s.is_contiguous() and r.numel() == s.numel()
+    lib = _hip.lib()
+    args = (len(running), _hip.ptr_array(running), _hip.ptr_array(stats), _hip.i64_array([r.numel() for r in running]),
+            _hip.f32_array([float(u) for u in unbias]), float(momentum), _hip.current_stream())
+    _hip.launch("bn_running_update", lambda: _hip.check(lib.savfi_bn_running_update_f32(*args), "savfi_bn_running_update_f32"))
+
+
+def max_pool2x2(x):
+    """nn.MaxPool2d(2, 2) of [N,C,H,W]: odd sides floor, NaN propagates as in torch.max_pool2d.  Forward only."""
+    x = x.contiguous()
+    _hip.require_cuda(x)
+    _frozen("max_pool2x2", x)
+    N, C, H, W = x.shape
+    out = x.new_empty(N, C, H // 2, W // 2)
+    lib = _hip.lib()
+    _hip.launch("maxpool2x2", lambda: _hip.check(lib.savfi_maxpool2x2_f32(
+        x.data_ptr(), out.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_maxpool2x2_f32"), nbytes=5 * out.numel() * 4)
+    return out
+
+
+def upnearest2x_add(low, skip):
+    """skip + UpsamplingNearest2d(scale_factor=2)(low): the hourglass's upsample and CAddTable in one pass.  Forward only."""
+    low, skip = low.contiguous(), skip.contiguous()
+    _hip.require_cuda(low, skip)
+    _frozen("upnearest2x_add", low, skip)
+    N, C, h, w = low.shape
+    if tuple(skip.shape) != (N, C, 2 * h, 2 * w):
+        raise ValueError("skip %s is not exactly twice low %s on both sides" % (tuple(skip.shape), tuple(low.shape)))
+    out = torch.empty_like(skip)
+    lib = _hip.lib()
+    _hip.launch("upnearest2x_add", lambda: _hip.check(lib.savfi_upnearest2x_add_f32(
+        low.data_ptr(), skip.data_ptr(), out.data_ptr(), N * C, h, w, 2 * h, 2 * w, _hip.current_stream()),
+        "savfi_upnearest2x_add_f32"), nbytes=9 * low.numel() * 4)
+    return out
+
+
+class _AddRelu(torch.autograd.Function):
+    """relu(a + r); the derivative, taken from the result, goes to both inputs."""
+
+    @staticmethod
+    def forward(ctx, a, r):
+        _hip.require_cuda(a, r)
+        assert a.shape == r.shape
+        y = torch.empty_like(a)
+        lib = _hip.lib()
+        _hip.launch("add_relu", lambda: _hip.check(lib.savfi_add_relu_f32(
+            a.data_ptr(), r.data_ptr(), y.data_ptr(), a.numel(), _hip.current_stream()), "savfi_add_relu_f32"), nbytes=12 * a.numel())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        shape = g.shape
+        g = mask_by_activation(g.reshape(1, 1, -1), y.reshape(1, 1, -1), 0.0).reshape(shape)
+        return g, g
+
+
+def add_relu(a, r):
+    """relu(a + r), the tail of a residual block (dain/Resblock/BasicBlock.py:146-147), one pass; first order."""
+    if double_backward():
+        return torch.relu(a + r)
+    return _AddRelu.apply(a.contiguous(), r.contiguous())
+
+
+class _Charbonnier(torch.autograd.Function):
+    """a, b [rows, ...] -> float32[rows] of per-row mean sqrt((a - b)^2 + eps^2); deterministic."""
+
+    @staticmethod
+    def forward(ctx, a, b, eps):
+        _hip.require_cuda(a, b)
+        assert a.shape == b.shape
+        rows = a.shape[0]
+        n = a.numel() // rows
+        res = torch.empty(rows, dtype=torch.float32, device=a.device)
+        scratch = torch.empty(_workspace_floats("savfi_l1_mse_scratch_floats", rows, n), dtype=torch.float32, device=a.device)
+        lib = _hip.lib()
+        _hip.launch("charbonnier", lambda: _hip.check(lib.savfi_charbonnier_f32(
+            a.data_ptr(), b.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, n, eps, _hip.current_stream()),
+            "savfi_charbonnier_f32"), nbytes=8 * a.numel())
+        ctx.eps = eps
+        ctx.save_for_backward(a, b)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        g = g.contiguous()
+        ga = torch.empty_like(a)
+        rows = a.shape[0]
+        lib = _hip.lib()
+        _hip.launch("charbonnier_bwd", lambda: _hip.check(lib.savfi_charbonnier_bwd_f32(
+            a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), rows, a.numel() // rows, ctx.eps, _hip.current_stream()),
+            "savfi_charbonnier_bwd_f32"), nbytes=12 * a.numel())
+        gb = -ga if ctx.needs_input_grad[1] else None
+        return ga, gb, None
+
+
+def charbonnier_loss(a, b, eps=CHARBONNIER_EPS):
+    """mean(sqrt((a - b)^2 + eps^2)) over everything (dain/loss_function.py:14-16)."""
+    if double_backward():
+        d = a - b
+        return torch.mean(torch.sqrt(d * d + eps * eps))
+    return _Charbonnier.apply(a.contiguous().reshape(1, -1), b.contiguous().reshape(1, -1), float(eps)).reshape(())
+
+
+def charbonnier_loss_per_sample(a, b, eps=CHARBONNIER_EPS):
+    """[N,...] x [N,...] -> [N]: the Charbonnier loss of every sample on its own, one launch."""
+    if double_backward():
+        d = a - b
+        return torch.sqrt(d * d + eps * eps).flatten(1).mean(1)
+    a, b = a.contiguous(), b.contiguous()
+    return _Charbonnier.apply(a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1), float(eps))
+
+
+# --------------------------------------------------------------------------------------------
 # conv + bias + (leaky) ReLU with fused epilogues   (sepconv/model.py:172-194, model_utils.py:957-990)
 # --------------------------------------------------------------------------------------------
 # 3x3 / stride 1 convolutions run on savfi_conv3x3_f32 (Winograd on the fp32 matrix cores, bias + activation in its

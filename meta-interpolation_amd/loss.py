@@ -50,3 +50,25 @@ class Loss(nn.modules.loss._Loss):
             total = total + eff
         losses['total'] = total
         return losses
+
+
+class CharbonnierLoss(nn.modules.loss._Loss):
+    """The criterion of --model dain whatever --loss says (reference meta_learning_system.py:493-505 with dain/networks/DAIN.py:638-639):
+    the Charbonnier loss of the unpadded rectified frame, ``{'DAIN': L, 'total': L}``.  The reference's sum also holds the term of the
+    unrectified frame with weight 0.0; it is not computed here."""
+
+    def __init__(self, eps=hip_ops.CHARBONNIER_EPS):
+        super().__init__()
+        self.eps = float(eps)
+        self.cuda_only = True
+
+    def loss_keys(self):
+        return ['DAIN', 'total']
+
+    def per_sample(self, sr, hr):
+        value = hip_ops.charbonnier_loss_per_sample(sr, hr, self.eps)
+        return {'DAIN': value, 'total': value}
+
+    def forward(self, sr, hr, **kwargs):
+        value = hip_ops.charbonnier_loss(sr, hr, self.eps)
+        return {'DAIN': value, 'total': value}

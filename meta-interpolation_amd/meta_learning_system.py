@@ -30,7 +30,7 @@ import torch.optim as optim
 
 from . import _hip, graph_inner_loop, hip_ops, model_utils, utils
 from .inner_loop_optimizers import LSLRGradientDescentLearningRule, MetaSGDLearningRule
-from .loss import Loss
+from .loss import CharbonnierLoss, Loss
 from .task_parallel import TaskParallel
 
 
@@ -69,8 +69,13 @@ def _build_superslomo(args, resume):
     return MetaSuperSloMo(torch.device('cuda') if args.cuda else torch.device('cpu'), resume=resume)
 
 
+def _build_dain(args, resume):
+    from .dain.networks.DAIN import MetaDAIN
+    return MetaDAIN(resume=resume)
+
+
 MODEL_REGISTRY = {'sepconv': _build_sepconv, 'cain': _build_cain, 'voxelflow': _build_voxelflow, 'rrin': _build_rrin,
-                  'superslomo': _build_superslomo}
+                  'superslomo': _build_superslomo, 'dain': _build_dain}
 
 
 def register_model(name, factory):
@@ -165,11 +170,12 @@ class SceneAdaptiveInterpolation(nn.Module):
         if net is not None:
             self.net = net.to(self.device)
         else:
+            if args.model == 'dain' and not args.cuda:
+                raise NotImplementedError("Model not implemented on the host! DAIN's two own ops (dain/my_package: "
+                                          "FilterInterpolationModule, DepthFlowProjectionModule), its flow estimator "
+                                          "(dain/PWCNet: PWCDCNet, Correlation) and the rest of the MetaDAIN plugin run on the HIP "
+                                          "kernels only: --model dain has no CPU path.")
             if args.model not in MODEL_REGISTRY:
-                if args.model == 'dain':
-                    raise NotImplementedError("Model not implemented yet! DAIN's two own ops exist (dain/my_package: "
-                                              "FilterInterpolationModule, DepthFlowProjectionModule) and so does its flow estimator "
-                                              "(dain/PWCNet: PWCDCNet, Correlation); the MetaDAIN plugin does not yet.")
                 raise NotImplementedError('Model not implemented yet!')
             print('Building %s model...' % args.model)
             self.net = MODEL_REGISTRY[args.model](args, not args.resume).to(self.device)
@@ -195,6 +201,9 @@ class SceneAdaptiveInterpolation(nn.Module):
                 total_num_inner_loop_steps=args.number_of_training_steps_per_iter,
                 use_learnable_learning_rates=args.learnable_per_layer_per_step_inner_loop_learning_rate)
 
+        if hasattr(self.net, 'freeze_front'):
+            # dain: everything outside rectifyNet is constant (reference :96-101) -- before the inner-loop dictionary is built
+            self.net.freeze_front()
         names_weights = self.get_inner_loop_parameter_dict(self.net.named_parameters())
         self.inner_loop_optimizer.initialize(names_weights_dict=names_weights)
 
@@ -221,7 +230,12 @@ class SceneAdaptiveInterpolation(nn.Module):
                                                               patience=5)
         print('# of parameters: %d' % sum(p.numel() for p in self.trainable_parameters()))
 
-        self.criterion = criterion if criterion is not None else Loss(args)
+        if criterion is not None:
+            self.criterion = criterion
+        elif args.model == 'dain':     # the network's own Charbonnier loss whatever --loss says (reference :493-505)
+            self.criterion = CharbonnierLoss()
+        else:
+            self.criterion = Loss(args)
         self.task_parallel = task_parallel if task_parallel is not None else TaskParallel()
         if self.device.type == 'cuda':
             with torch.cuda.device(self.device):
@@ -242,7 +256,9 @@ class SceneAdaptiveInterpolation(nn.Module):
             print('Loading pretrained model: %s' % args.pretrained_model)
             ckpt = torch.load(args.pretrained_model, map_location='cpu', weights_only=False)
             with torch.no_grad():
-                if 'state_dictFC' in ckpt:       # Super SloMo's released checkpoints (reference :162-167)
+                if args.model == 'dain':         # the bare state dict (reference :168-169)
+                    utils.lossy_load_state_dict(self.net, ckpt)
+                elif 'state_dictFC' in ckpt:     # Super SloMo's released checkpoints (reference :162-167)
                     self.net.flowComp.load_state_dict(ckpt['state_dictFC'])
                     self.net.arbTimeFlowIntrp.load_state_dict(ckpt['state_dictAT'])
                 else:
@@ -289,16 +305,26 @@ class SceneAdaptiveInterpolation(nn.Module):
     # -----------------------------------------------------------------------------------------
     # forward passes
     # -----------------------------------------------------------------------------------------
-    def net_forward(self, frame0, frame1, target, weights, backup_running_statistics, training, num_step):
+    def _front_kw(self, fronts, key, frame0, frame1):
+        """A plugin with a frozen front (dain: everything before its rectify net is a function of the frames and of constants)
+        evaluates it once per task and triplet and meta-iteration: `fronts` is the task's own {triplet: front}, `key` names the
+        triplet.  -> the keyword that hands it to the plugin's forward, or nothing (no such plugin; reuse switched off)."""
+        if fronts is None or not getattr(self.net, 'reuse_front', False):
+            return {}
+        if key not in fronts:
+            fronts[key] = self.net.front(frame0, frame1)
+        return {'front': fronts[key]}
+
+    def net_forward(self, frame0, frame1, target, weights, backup_running_statistics, training, num_step, front_kw=None):
         """One backbone pass with fast weights + criterion -> (losses dict, output)  (reference :475-509)."""
         output = self.net.forward(frame0, frame1, params=weights,
-                                  backup_running_statistics=backup_running_statistics, num_step=num_step)
+                                  backup_running_statistics=backup_running_statistics, num_step=num_step, **(front_kw or {}))
         if isinstance(output, tuple):     # superslomo: (frame, flows and warped frames for the 'Super' loss)  (:499-502)
             output, extras = output
             return self.criterion(output, target, I0=frame0, I1=frame1, **extras), output
         return self.criterion(output, target), output
 
-    def _support_loss(self, frames, task_id, weights, num_step):
+    def _support_loss(self, frames, task_id, weights, num_step, fronts=None):
         """Sum of the two support-triplet losses of one inner step (reference :387-396)."""
         a, b = self.support_idxs
         # step 0 differentiates w.r.t. theta itself, whose non-routed tensors ARE the modules' own parameters
@@ -309,45 +335,47 @@ class SceneAdaptiveInterpolation(nn.Module):
         hip_ops.set_weight_gradient_overlap(self._first_order and self.device.type == 'cuda'
                                             and bool(getattr(self.args, 'wgrad_overlap', 0)))
         try:
-            return self._support_loss_impl(frames, task_id, weights, num_step, a, b)
+            return self._support_loss_impl(frames, task_id, weights, num_step, a, b, fronts)
         finally:
             model_utils.set_own_params_const(False)
             hip_ops.set_weight_gradient_overlap(False)
 
-    def _support_loss_impl(self, frames, task_id, weights, num_step, a, b):
+    def _support_loss_impl(self, frames, task_id, weights, num_step, a, b, fronts=None):
         if self.fuse_support_pairs:
             sl = slice(task_id, task_id + 1)
             f0 = torch.cat([frames[a[0]][sl], frames[b[0]][sl]], 0)
             f1 = torch.cat([frames[a[2]][sl], frames[b[2]][sl]], 0)
             out = self.net.forward(f0, f1, params=weights, backup_running_statistics=(num_step == 0),
-                                   num_step=num_step)
+                                   num_step=num_step, **self._front_kw(fronts, 'support', f0, f1))
             if isinstance(out, tuple):    # superslomo; its extras only feed the 'Super' loss, which Loss rejects
                 out = out[0]
             la = self.criterion(out[0:1], frames[a[1]][sl])
             lb = self.criterion(out[1:2], frames[b[1]][sl])
             return la['total'] + lb['total']
         total = 0
-        for ind in (a, b):
-            losses, _ = self.net_forward(frame0=frames[ind[0]][task_id].unsqueeze(0),
-                                         frame1=frames[ind[2]][task_id].unsqueeze(0),
+        for which, ind in enumerate((a, b)):
+            f0, f1 = frames[ind[0]][task_id].unsqueeze(0), frames[ind[2]][task_id].unsqueeze(0)
+            losses, _ = self.net_forward(frame0=f0, frame1=f1,
                                          target=frames[ind[1]][task_id].unsqueeze(0), weights=weights,
                                          backup_running_statistics=(num_step == 0), training=True,
-                                         num_step=num_step)
+                                         num_step=num_step, front_kw=self._front_kw(fronts, 'support%d' % which, f0, f1))
             total = total + losses['total']
         return total
 
-    def _target_pass(self, frames, task_id, weights, num_step):
+    def _target_pass(self, frames, task_id, weights, num_step, fronts=None):
         t = self.target_idxs
-        return self.net_forward(frame0=frames[t[0]][task_id].unsqueeze(0), frame1=frames[t[2]][task_id].unsqueeze(0),
+        f0, f1 = frames[t[0]][task_id].unsqueeze(0), frames[t[2]][task_id].unsqueeze(0)
+        return self.net_forward(frame0=f0, frame1=f1,
                                 target=frames[t[1]][task_id].unsqueeze(0), weights=weights,
-                                backup_running_statistics=False, training=True, num_step=num_step)
+                                backup_running_statistics=False, training=True, num_step=num_step,
+                                front_kw=self._front_kw(fronts, 'target', f0, f1))
 
     # -----------------------------------------------------------------------------------------
     # L2F
     # -----------------------------------------------------------------------------------------
-    def get_task_embeddings(self, frames, task_id, names_weights_copy):
+    def get_task_embeddings(self, frames, task_id, names_weights_copy, fronts=None):
         """Layer-wise mean of the support gradient at theta (reference :231-255), one fused reduction."""
-        loss = self._support_loss(frames, task_id, names_weights_copy, num_step=0)
+        loss = self._support_loss(frames, task_id, names_weights_copy, num_step=0, fronts=fronts)
         self.net.zero_grad(names_weights_copy)
         grads = torch.autograd.grad(loss, names_weights_copy.values(), create_graph=False, allow_unused=True)
         hip_ops.join_weight_gradients()
@@ -378,16 +406,16 @@ class SceneAdaptiveInterpolation(nn.Module):
             names_grads_wrt_params_dict=dict(zip(names_weights_copy.keys(), grads)),
             num_step=current_step_idx)
 
-    def _adapt(self, frames, task_id, num_steps, use_second_order, per_step_hook=None):
-        """Run the inner loop of one task; returns the adapted fast weights."""
+    def _adapt(self, frames, task_id, num_steps, use_second_order, per_step_hook=None, fronts=None):
+        """Run the inner loop of one task; returns the adapted fast weights.  fronts: the task's {triplet: front} (_front_kw)."""
         weights = self.get_inner_loop_parameter_dict(self.net.named_parameters())
         weights = {name.replace('module.', ''): v for name, v in weights.items()}
         self.inner_loop_optimizer.initialize_state()
         if self.args.attenuate:
-            emb = self.get_task_embeddings(frames, task_id, weights)
+            emb = self.get_task_embeddings(frames, task_id, weights, fronts)
             weights = self.attenuate_init(task_embeddings=emb, names_weights_copy=weights)
         for num_step in range(num_steps):
-            support_loss = self._support_loss(frames, task_id, weights, num_step)
+            support_loss = self._support_loss(frames, task_id, weights, num_step, fronts)
             weights = self.apply_inner_loop_update(loss=support_loss, names_weights_copy=weights,
                                                    use_second_order=use_second_order, current_step_idx=num_step)
             if per_step_hook is not None:
@@ -410,23 +438,24 @@ class SceneAdaptiveInterpolation(nn.Module):
         """Everything one task contributes to a meta-iteration (reference :366-461): adaptation, target pass(es), its
         loss term, prediction, logging scalars.  Touches no shared mutable state, so tasks can run concurrently."""
         task_losses, logs, state = [], [], {}
+        fronts = {} if hasattr(self.net, 'front') else None       # this task's frozen fronts, one per triplet (dain)
 
         def after_step(num_step, weights):
             if msl:  # MAML++: weighted target loss after every inner step
-                tl, tp_ = self._target_pass(frames, task_id, weights, num_step)
+                tl, tp_ = self._target_pass(frames, task_id, weights, num_step, fronts)
                 task_losses.append(importance[num_step] * tl['total'])
                 logs.extend(tl.items())
                 state['preds'] = tp_
 
-        weights = self._adapt(frames, task_id, num_steps, use_second_order, after_step)
+        weights = self._adapt(frames, task_id, num_steps, use_second_order, after_step, fronts)
 
         if not training_phase:
             with torch.no_grad():
-                tl, state['preds'] = self._target_pass(frames, task_id, weights, num_steps)
+                tl, state['preds'] = self._target_pass(frames, task_id, weights, num_steps, fronts)
             task_losses.append(tl['total'])
             logs.extend(tl.items())
         elif not msl:
-            tl, state['preds'] = self._target_pass(frames, task_id, weights, num_steps)
+            tl, state['preds'] = self._target_pass(frames, task_id, weights, num_steps, fronts)
             task_losses.append(tl['total'])
             logs.extend(tl.items())
 
@@ -963,7 +992,7 @@ class SceneAdaptiveInterpolation(nn.Module):
         try:
             for task_id in range(len(frames[0])):
                 steps = self.args.number_of_evaluation_steps_per_iter
-                weights = self._adapt(frames, task_id, steps, False)
+                weights = self._adapt(frames, task_id, steps, False, fronts={} if hasattr(self.net, 'front') else None)
                 with torch.no_grad():
                     out = self.net.forward(frames[1][task_id].unsqueeze(0), frames[2][task_id].unsqueeze(0),
                                            params=weights, backup_running_statistics=False,
