@@ -76,7 +76,8 @@ extern "C" {
  * (a binding written for the older header still works).  Added under 24: savfi_correlation_fwd_f32, savfi_correlation_bwd_f32,
  * savfi_pwcwarp_fwd_f32; then, for DAIN's frozen front and rectify net, savfi_bn_stats_scratch_floats, savfi_bn_stats_f32,
  * savfi_bn_apply_relu_f32, savfi_bn_running_update_f32, savfi_maxpool2x2_f32, savfi_upnearest2x_add_f32, savfi_add_relu_f32,
- * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32. */
+ * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32; then savfi_conv3x3_f4_launched_workgroups, savfi_conv3x3_debug_f4_block_decode,
+ * savfi_conv3x3_tasks_pre_pool_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -441,6 +442,14 @@ int64_t savfi_conv3x3_filter_floats(int T, int Ci, int Co, int mode);
  * kernel would launch for this call (32 tiles of 4 x 4 pixels x 32 produced channels each, x the reduction split of a deep layer on a
  * small map), 0 for an F(2x2) layer -- a caller with another kernel for launches that cannot fill the chip routes by this count. */
 int64_t savfi_conv3x3_f4_workgroups(int N, int Ci, int Co, int H, int W, int pad, int mode);
+/* The grid an F(4x4) launch of this call really has: each sample's row-major tile list is cut into groups of 32, so ceil(tiles / 32)
+ * workgroups per sample, reduction split and 32-channel block -- fewer than the block count above on maps whose tile counts are no
+ * powers of two (65 x 113 tiles: 230 against 255).  savfi_conv3x3_f4_workgroups keeps counting 2^(5-s) x 2^s tile BLOCKS: callers route
+ * by it and routing does not move.  0 for an F(2x2) layer. */
+int64_t savfi_conv3x3_f4_launched_workgroups(int N, int Ci, int Co, int H, int W, int pad, int mode);
+/* Test hook: on != 0 makes the F(4x4) launches issued afterwards decode tiles by blocks again (the grid savfi_conv3x3_f4_workgroups
+ * counts); 0 restores the flat tile lists.  Same results bit for bit either way.  *previous (may be NULL) receives the old setting. */
+int savfi_conv3x3_debug_f4_block_decode(int on, int* previous);
 /* The caller's choice of the form per layer AND map: bit 1 of every `mode` argument of the savfi_conv3x3_* functions (mode | 2) and `form`
  * = 2 below select the F(2x2) kernel whatever the channel counts -- for launches too small for F(4x4) to pay (it rounds 5x coarser; an
  * Adam-type inner rule turns that into flipped steps of elements whose gradient is rounding noise).  form = 0 / bit clear: by the channel
@@ -457,6 +466,13 @@ int savfi_conv3x3_filters_multi_f32(const float* const* w, float* const* u_fwd, 
 int64_t savfi_conv3x3_tasks_pre_workspace_floats(int N, int T, int Ci, int Co, int H, int W, int pad, int mode);
 int savfi_conv3x3_tasks_pre_f32(const float* x, const float* u, const float* bias, float* out, float* workspace,
                                 int N, int T, int Ci, int Co, int H, int W, int pad, int mode, float slope, void* stream);
+/* savfi_conv3x3_tasks_pre_f32 for a layer whose activated result is average-pooled 2 x 2 right away (an encoder block's last layer).
+ * pooled [N][channels of out][Ho / 2][Wo / 2] (floor sizes, as savfi_avgpool2x2_fwd_f32).  *did_pool = 1: the convolution's output
+ * stage wrote it -- the values savfi_avgpool2x2_fwd_f32 computes from `out`, bit for bit, without reading `out` back; *did_pool = 0
+ * (the F(2x2) form, a split reduction, an odd output width, a data gradient): `pooled` is untouched and the caller pools `out` itself. */
+int savfi_conv3x3_tasks_pre_pool_f32(const float* x, const float* u, const float* bias, float* out, float* pooled, float* workspace,
+                                     int N, int T, int Ci, int Co, int H, int W, int pad, int mode, float slope, int* did_pool,
+                                     void* stream);
 /* Data gradient (mode 1) on a transformed filter with the (leaky) ReLU derivative of the layer that PRODUCED this convolution's input
  * folded into the output stage: gx = dgrad(gy) * (mask > 0 ? 1 : mask_slope); mask [N,Ci,H+2-2pad,W+2-2pad] is the convolution's
  * forward input (= the producer's activated output).  conv -> ReLU -> conv chains (sepconv/model.py:172-245 Basic / Subnet blocks):

@@ -87,12 +87,15 @@ _PROTOTYPES = {
     "savfi_conv3x3_tasks_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P],
     "savfi_conv3x3_filter_floats": [c_int] * 4,
     "savfi_conv3x3_f4_workgroups": [c_int] * 7,
+    "savfi_conv3x3_f4_launched_workgroups": [c_int] * 7,
+    "savfi_conv3x3_debug_f4_block_decode": [c_int, POINTER(c_int)],
     "savfi_conv3x3_filters_form_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_filters_multi_form_f32": [_P, _P, _P, _P, _P, _P, _P, c_int, _P],
     "savfi_conv3x3_dgrad_masked_form_f32": [_P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_filters_f32": [_P, _P, _P, c_int, c_int, c_int, _P],
     "savfi_conv3x3_tasks_pre_workspace_floats": [c_int] * 8,
     "savfi_conv3x3_tasks_pre_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P],
+    "savfi_conv3x3_tasks_pre_pool_f32": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, POINTER(c_int), _P],
     "savfi_conv3x3_unit16_supported": [c_int] * 7,
     "savfi_conv3x3_in_unit16_supported": [c_int] * 7,
     "savfi_conv3x3_dgrad_in_unit16_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],

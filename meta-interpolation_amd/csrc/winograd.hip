@@ -649,6 +649,7 @@ int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 struct WinoPlan {
   int K, I, KP, IP, off, Ho, Wo, th, tw, tile_shift, nsplit, chunks_per_split;
+  int ty4, tx4;       // F(4x4): the map's 4 x 4 tiles (th x tw: its tile BLOCKS, what routing counts by)
   int64_t u_floats, partial_floats;
   bool f4;            // Winograd F(4x4, 3x3) (winograd4.h): 4x4-pixel tiles, 32 per workgroup, no reduction split
 };
@@ -695,6 +696,8 @@ bool make_plan(WinoPlan& p, int N, int Ci, int Co, int H, int W, int pad, int mo
     }
     p.th = savfi_cdiv(ty4, w4::TT >> p.tile_shift);
     p.tw = savfi_cdiv(tx4, 1 << p.tile_shift);
+    p.ty4 = ty4;
+    p.tx4 = tx4;
     // deep layers on small maps: the reduction chunks split over workgroups where the launch would leave most of the 512 workgroup slots
     // empty (at least 4 chunks = 32 channels per workgroup); raw partial outputs, summed by wino_split_reduce
     const int nchunk4 = p.KP / w4::KC;
@@ -776,6 +779,28 @@ extern "C" int64_t savfi_conv3x3_f4_workgroups(int N, int Ci, int Co, int H, int
   return p.f4 ? (int64_t)p.th * p.tw * (p.IP / w4::COB) * p.nsplit * N : 0;
 }
 
+// F(4x4) launches walk each sample's row-major tile list 32 tiles per workgroup: ceil(tiles / 32) workgroups per (sample, split, channel
+// block), where the best 2^(5-s) x 2^s block shape leaves empty slots on maps whose tile counts are no powers of two (65 x 113 tiles:
+// 255 blocks, 230 flat).  savfi_conv3x3_f4_workgroups above keeps counting blocks -- routing was measured with those numbers and does
+// not move --; this is the grid a launch really has.  The debug setter brings the block decode back (same results bit for bit: a tile's
+// arithmetic does not depend on the workgroup it sits in) so that tests can compare the two.
+static int w4_block_decode = 0;
+static int64_t w4_tile_groups(const WinoPlan& p) {
+  return w4_block_decode ? (int64_t)p.th * p.tw : ((int64_t)p.ty4 * p.tx4 + w4::TT - 1) / w4::TT;
+}
+extern "C" int64_t savfi_conv3x3_f4_launched_workgroups(int N, int Ci, int Co, int H, int W, int pad, int mode) {
+  if (N <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return SAVFI_E_SHAPE;
+  if ((mode & ~3) || (pad != 0 && pad != 1)) return SAVFI_E_UNSUPPORTED;
+  WinoPlan p;
+  if (!make_plan(p, N, Ci, Co, H, W, pad, mode)) return SAVFI_E_SHAPE;
+  return p.f4 ? w4_tile_groups(p) * (p.IP / w4::COB) * p.nsplit * N : 0;
+}
+extern "C" int savfi_conv3x3_debug_f4_block_decode(int on, int* previous) {
+  if (previous) *previous = w4_block_decode;
+  w4_block_decode = on ? 1 : 0;
+  return SAVFI_OK;
+}
+
 extern "C" int64_t savfi_conv3x3_workspace_floats(int N, int Ci, int Co, int H, int W, int pad, int mode) {
   return savfi_conv3x3_tasks_workspace_floats(N, 1, Ci, Co, H, W, pad, mode);
 }
@@ -784,30 +809,42 @@ namespace {
 
 // launches one wino4_conv3x3 instantiation; each has its own flag of the devices its 72 KB dynamic-LDS attribute is set on (one static
 // in a generic lambda shared by all instantiations -- they have one function type -- configured only the first one launched)
-template <int VECW, int IN16, bool MASK>
+template <int VECW, int IN16, bool MASK, bool POOL = false>
 int launch_wino4(const w4::W4Args& a4, int64_t wgs4, hipStream_t st) {
   static uint32_t configured = 0;
   constexpr size_t lds4 = (size_t)w4::LDS_FLOATS * sizeof(float);      // 72 KB: two workgroups per CU
-  auto kern = w4::wino4_conv3x3<VECW, IN16, MASK>;
+  auto kern = w4::wino4_conv3x3<VECW, IN16, MASK, POOL>;
   if (int rc = savfi_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds4, configured)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs4), dim3(256), lds4, st, a4);
   return savfi_launch_status();
 }
 
+// can this launch's output stage store the 2 x 2 average pool of its result as well (winograd4.h, POOL)?  A forward on the F(4x4) kernel
+// with the planar, unsplit epilogue and row stores of 4 or 2 floats -- an odd width keeps the separate pooling kernel
+bool pools_in_epilogue(const WinoPlan& p, int mode) {
+  return p.f4 && (mode & 1) == 0 && p.nsplit == 1 && p.Wo % 2 == 0 && p.Ho >= 2;
+}
+
 // launches wino_conv3x3 (+ the split reduction) on an already transformed filter U [T][16 * KP * IP]
+// pooled != NULL: the caller has asked pools_in_epilogue
 int launch_conv(const WinoPlan& p, const float* x, const float* U, const float* bias, float* out, float* partial, int N, int T,
                 int H, int W, int mode, float slope, hipStream_t st, const float* mask = nullptr, float mask_slope = 1.f,
-                int out_unit16 = 0, int in_unit16 = 0) {
+                int out_unit16 = 0, int in_unit16 = 0, float* pooled = nullptr) {
+  if (pooled && (!pools_in_epilogue(p, mode) || mask || out_unit16 || in_unit16)) return SAVFI_E_UNSUPPORTED;
   if (p.f4) {
-    const int64_t wgs4 = (int64_t)p.th * p.tw * (p.IP / w4::COB) * p.nsplit * N;
+    const int64_t ntb = w4_tile_groups(p);
+    const int64_t wgs4 = ntb * (p.IP / w4::COB) * p.nsplit * N;
     if (wgs4 > 0x7fffffffLL || T > 65535) return SAVFI_E_TOOBIG;
     if (mask && (out_unit16 || in_unit16)) return SAVFI_E_UNSUPPORTED;
     if (p.nsplit > 1 && (out_unit16 || in_unit16 || !partial)) return SAVFI_E_UNSUPPORTED;
     if (in_unit16 && ((p.off != 1 && p.off != 2) || p.Wo % 2 != 0)) return SAVFI_E_UNSUPPORTED;
     w4::W4Args a4{x, U, (mode & 1) == 0 ? bias : nullptr, out, p.K, p.I, p.KP, p.IP, H, W, p.Ho, p.Wo, p.off, p.th, p.tw, slope,
-                  p.tile_shift, T, N, p.nsplit > 1 ? nullptr : mask, mask_slope, out_unit16, p.nsplit, p.chunks_per_split, partial};
+                  p.tile_shift, T, N, p.nsplit > 1 ? nullptr : mask, mask_slope, out_unit16, p.nsplit, p.chunks_per_split, partial,
+                  w4_block_decode ? 0 : 1, p.ty4, p.tx4, (int)ntb, p.tx4 > 1 ? (unsigned)(0x100000000ull / (unsigned)p.tx4) : 0xffffffffu,
+                  pooled, p.Ho / 2, p.Wo / 2};
     const int vecw = p.Wo % 4 == 0 ? 4 : (p.Wo % 2 == 0 ? 2 : 1);
     auto go = [&](auto kern) { return kern(a4, wgs4, st); };
+    if (pooled) return vecw == 4 ? go(launch_wino4<4, 0, false, true>) : go(launch_wino4<2, 0, false, true>);
     if (in_unit16 && p.off == 1) return vecw == 4 ? go(launch_wino4<4, 2, false>) : go(launch_wino4<2, 2, false>);
     if (in_unit16) return vecw == 4 ? go(launch_wino4<4, 3, false>) : go(launch_wino4<2, 3, false>);
     if (p.nsplit > 1) {
@@ -964,6 +1001,22 @@ extern "C" int savfi_conv3x3_tasks_pre_f32(const float* x, const float* u, const
   if (int e = check_conv_args(p, N, T, Ci, Co, H, W, pad, mode)) return e;
   if (p.partial_floats > 0 && !workspace) return SAVFI_E_NULL;
   return launch_conv(p, x, u, bias, out, workspace, N, T, H, W, mode, slope, (hipStream_t)stream);
+}
+
+// savfi_conv3x3_tasks_pre_f32 for a layer whose activated result is average-pooled 2 x 2 right away (an encoder block's last layer):
+// `pooled` [N][Co or Ci][Ho / 2][Wo / 2] (floor sizes, as savfi_avgpool2x2_fwd_f32) is written by the convolution's output stage where
+// that is possible -- *did_pool = 1, the values savfi_avgpool2x2_fwd_f32 gives on `out`, bit for bit -- and left untouched otherwise
+// (*did_pool = 0: the F(2x2) form, a split reduction, an odd width, a data gradient): the caller then runs the pooling kernel itself.
+extern "C" int savfi_conv3x3_tasks_pre_pool_f32(const float* x, const float* u, const float* bias, float* out, float* pooled, float* workspace,
+                                                int N, int T, int Ci, int Co, int H, int W, int pad, int mode, float slope, int* did_pool,
+                                                void* stream) {
+  if (!x || !u || !out || !pooled || !did_pool) return SAVFI_E_NULL;
+  WinoPlan p;
+  if (int e = check_conv_args(p, N, T, Ci, Co, H, W, pad, mode)) return e;
+  if (p.partial_floats > 0 && !workspace) return SAVFI_E_NULL;
+  // (the pooled planes ride in one descriptor per sample like the output's: smaller, so check_conv_args has bounded them)
+  *did_pool = pools_in_epilogue(p, mode) ? 1 : 0;
+  return launch_conv(p, x, u, bias, out, workspace, N, T, H, W, mode, slope, (hipStream_t)stream, nullptr, 1.f, 0, 0, *did_pool ? pooled : nullptr);
 }
 
 // savfi_conv3x3_tasks_pre_f32, forward only, with the result written UNIT-MAJOR: out[n] is [Ho][Wo / 16][Co][16] instead of [Co][Ho][Wo] --

@@ -13,7 +13,7 @@
 //   Y = A^T [ (G g G^T) (.) (B^T d B) ] A        per 4x4 output tile, d = its 6x6 input patch
 //   M[xi][i][t] = sum_k U[xi][k][i] V[xi][k][t]   36 GEMMs on v_mfma_f32_16x16x4_f32   (k: reduction channel, i: produced)
 //
-// Workgroup = 4 waves, two per CU (73.7 KB LDS, <= 256 registers): 32 tiles (a 2^(5-s) x 2^s block = 512 output pixels) x 32
+// Workgroup = 4 waves, two per CU (73.7 KB LDS, <= 256 registers): 32 tiles (consecutive in the sample's row-major tile list) x 32
 // produced channels; wave w owns Winograd points 9w .. 9w+8 for all of them (9 x 2 x 2 accumulator tiles = 144 registers) and
 // walks the reduction channels 8 at a time (two MFMA k-steps, 72 MFMAs).  Per chunk every thread transforms ONE 6x6 patch
 // (tile = lane % 32, channel = 2 wave + lane / 32): first pass over the patch rows for TWO columns at once on packed fp32
@@ -142,6 +142,14 @@ struct W4Args {
   int out_unit16;
   int nsplit, chunks_per_split;       // reduction chunks split over workgroups (deep layers on small maps): raw partial outputs
   float* partial;                     // [split][N][I][Ho][Wo], summed (+ bias, activation, mask) by wino_split_reduce
+  // Tile decode.  flat != 0: workgroup tb of a sample owns tiles 32 tb .. 32 tb + 31 of the sample's ROW-MAJOR list of ty4 x tx4 tiles
+  // (ntb = ceil(ty4 tx4 / 32) workgroups; only the last one has empty slots); tx_mul = floor(2^32 / tx4) (tx4 = 1: 2^32 - 1) divides by tx4.
+  // flat == 0: a 2^(5-s) x 2^s block per workgroup, tiles_y x tiles_x (= ntb) blocks -- the decode routing counts by, kept for comparison.
+  int flat, ty4, tx4, ntb;
+  unsigned tx_mul;
+  // POOL instances: the 2 x 2 average of the ACTIVATED output as well, planar [N][I][Hp][Wp] with Hp = Ho / 2, Wp = Wo / 2 (floor)
+  float* pooled;
+  int Hp, Wp;
 };
 
 __device__ __forceinline__ i32x4 w4_rsrc(const void* base, unsigned bytes) {
@@ -205,21 +213,23 @@ __device__ __forceinline__ void at6p(f32x2 m0, f32x2 m1, f32x2 m2, f32x2 m3, f32
 
 // VECW: elements per row store (4: Wo % 4 == 0, 2: Wo even, 1); IN16 = 1 + off (1 or 2): the input is unit-major ([y][x / 16][channel][16],
 // W % 16 == 0; 0: planar) -- column `off` of a patch row is then 16-byte aligned inside a unit: one 16-byte load + the two columns beside it;
-// MASK: out *= (mask > 0 ? 1 : mask_slope), mask laid out like the planar output (64 more registers: its own instance)
-template <int VECW, int IN16, bool MASK>
+// MASK: out *= (mask > 0 ? 1 : mask_slope), mask laid out like the planar output (64 more registers: its own instance);
+// POOL: the output stage also stores avgpool2x2 of what it stores (an encoder block's last layer: csrc/avgpool.hip's expression and order,
+// (((a + b) + c) + d) / 4, on the values in registers -- the separate kernel read the whole map back for it).  VECW 4 / 2, planar, no split.
+template <int VECW, int IN16, bool MASK, bool POOL = false>
 __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kg = lane >> 4;
 
-  // work item: [sample][tile block][channel block], channel block fastest; one XCD walks a contiguous eighth (winograd.hip): the workgroups
+  // work item: [sample][tile group][channel block], channel block fastest; one XCD walks a contiguous eighth (winograd.hip): the workgroups
   // that read the same input tiles run side by side on one XCD's L2 (tile block fastest, the first version: 51 -> 51 @258x450 777 / 928 us
   // forward / data gradient against 752 / 886, 64 -> 64 @192x256 93 against 90.5; the transformed filters are L2-resident either way)
   const int nblk = a.IP / COB;
   int tb, cob, n, sp;
   {
     const unsigned flat = blockIdx.x, nwg = gridDim.x;
-    const unsigned ntb = (unsigned)(a.tiles_y * a.tiles_x);
+    const unsigned ntb = (unsigned)a.ntb;
     const unsigned xcd = flat & 7u, q8 = nwg >> 3, rem = nwg & 7u;
     unsigned item = xcd * q8 + min(xcd, rem) + (flat >> 3);
     cob = (int)(item % (unsigned)nblk);
@@ -229,16 +239,38 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
     sp = (int)(item % (unsigned)a.nsplit);
     n = (int)(item / (unsigned)a.nsplit);
   }
-  const int tby = tb / a.tiles_x, tbx = tb - tby * a.tiles_x;
   const int i0 = cob * COB;
   const int task = a.T > 1 ? n % a.T : 0;
   const size_t cplane = (size_t)a.H * a.W;
   const float* xp = a.x + (size_t)n * a.K * cplane;
-  const int tsh = a.tile_shift, tbw = 1 << tsh, tbh = TT >> tsh;
+
+  // This thread's tile (row ty, column tx of the map's 4 x 4 tiles) is the same in the transform role (slot lane % 32) and in the output
+  // role (slot tid % 32).  ONE wave-uniform branch; everything else works from the per-lane tile.  A slot behind the list's last tile is
+  // not live: the roles put its rows below the map, so every load offset of it is the out-of-range 0x80000000 (it reads zeros) and its
+  // stores are dropped.
+  const int tl = lane & 31;
+  auto tile_of = [&](int tbq, int& ty, int& tx) {
+    if (a.flat) {
+      const unsigned t = 32u * (unsigned)tbq + (unsigned)tl, tx4 = (unsigned)a.tx4;
+      unsigned q = __umulhi(t, a.tx_mul);          // floor(t / tx4) or one less (t tx_mul / 2^32 > t / tx4 - 1)
+      unsigned r = t - q * tx4;
+      if (r >= tx4) { ++q; r -= tx4; }
+      ty = (int)q;
+      tx = (int)r;
+      return t < (unsigned)a.ty4 * tx4;
+    }
+    const int tsh = a.tile_shift, tbw = 1 << tsh, tbh = TT >> tsh;
+    const int tby = tbq / a.tiles_x, tbx = tbq - tby * a.tiles_x;
+    ty = tby * tbh + (tl >> tsh);
+    tx = tbx * tbw + (tl & (tbw - 1));
+    return true;
+  };
 
   // ---- transform role: tile tl, channel kc of the chunk ----
-  const int tl = lane & 31, kc = 2 * w + (lane >> 5);
-  const int y0 = 4 * (tby * tbh + (tl >> tsh)) - a.off, x0 = 4 * (tbx * tbw + (tl & (tbw - 1))) - a.off;
+  const int kc = 2 * w + (lane >> 5);
+  int tyi, txi;
+  const bool live = tile_of(tb, tyi, txi);
+  const int y0 = live ? 4 * tyi - a.off : a.H, x0 = live ? 4 * txi - a.off : 0;
   constexpr int WC = IN16 ? IN16 - 1 : 0;       // first column of a row's 16-byte load
   unsigned pv[6], pn[IN16 ? 6 : 1], pn2[IN16 == 2 ? 6 : 1];
   unsigned long long shl = 0, colm[6] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
@@ -274,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
     const unsigned long long all = __builtin_amdgcn_ballot_w64(true);
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-      colm[c] = __builtin_amdgcn_ballot_w64(x0 + c >= 0 && x0 + c < a.W);
+      colm[c] = __builtin_amdgcn_ballot_w64(!live || (x0 + c >= 0 && x0 + c < a.W));      // (an empty slot read zeros: nothing to clear)
       if (colm[c] != all) partial |= 1 << c;      // (bit c: some lane of this wave must clear column c)
     }
   }
@@ -478,7 +510,15 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
 
   // this thread finishes pairs p = tid + 256 qq of a round: tile p % 32 (= tid % 32), channel p / 32 of the round's 16
   const int otl = tid & 31, och = tid >> 5;
-  const int oy = 4 * (tby * tbh + (otl >> tsh)), ox = 4 * (tbx * tbw + (otl & (tbw - 1)));
+  // (otl == tl.)  Decoded again, not held in two more registers through the channel loop -- except in the MASK instances, whose tightest
+  // spot is this stage (64 mask values): measured per instance on the compiler's spill counts, DESIGN.md 4i
+  int tbo = tb, oty = tyi, otx = txi;
+  bool olive = live;
+  if constexpr (!MASK) {
+    asm volatile("" : "+s"(tbo));
+    olive = tile_of(tbo, oty, otx);
+  }
+  const int oy = olive ? 4 * oty : a.Ho, ox = 4 * otx;    // a slot behind the last tile stores nothing
   const unsigned oplane = (unsigned)(a.Ho * a.Wo) * 4u;
   constexpr int NS = 4 / VECW;                     // stores per row
   unsigned ooff[4][NS];
@@ -492,11 +532,26 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
       else ooff[r][e] = ok ? (unsigned)((oy + r) * a.Wo + x) * 4u + (unsigned)(lane >> 5) * oplane : 0x80000000u;
     }
   // planar: a descriptor over the wave's two channel planes of a pair (och = 2 w + lane / 32); a channel beyond I shrinks it
-  auto pair_rsrc = [&](const float* base, int cb, int qq) {
+  auto pair_rsrc = [&](const float* base, int cb, int qq, unsigned plane_bytes = 0) {
+    if (plane_bytes == 0) plane_bytes = oplane;
     const int ie = i0 + 16 * cb + 2 * w + 8 * qq;        // the wave's even channel
     const int have = a.I - ie < 0 ? 0 : (a.I - ie > 2 ? 2 : a.I - ie);
-    return w4_rsrc(base + ((size_t)n * a.I + (ie < a.I ? ie : 0)) * a.Ho * a.Wo, (unsigned)have * oplane);
+    return w4_rsrc(base + ((size_t)n * a.I + (ie < a.I ? ie : 0)) * (plane_bytes >> 2), (unsigned)have * plane_bytes);
   };
+  // POOL: the tile's 2 x 2 pooled pixels, rows oy / 2 + {0, 1}, columns ox / 2 + {0, 1}; VECW 4: Wp is even, a row's two are one 8-byte
+  // store (inside or outside the pooled map together); VECW 2: a dword each.  A pixel outside the floor-sized map is dropped.
+  constexpr int PS = VECW == 4 ? 1 : 2;
+  const unsigned pplane = POOL ? (unsigned)(a.Hp * a.Wp) * 4u : 0u;
+  unsigned poff[POOL ? 2 : 1][POOL ? PS : 1];
+  if constexpr (POOL) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int e = 0; e < PS; ++e) {
+        const int py = (oy >> 1) + r, px = (ox >> 1) + e;
+        poff[r][e] = (py < a.Hp && px < a.Wp) ? (unsigned)(py * a.Wp + px) * 4u + (unsigned)(lane >> 5) * pplane : 0x80000000u;
+      }
+  }
   float mk[MASK ? 2 : 1][MASK ? 2 : 1][4][4];
   if constexpr (MASK) {          // every mask value before the first store (one in-order counter for loads and stores)
 #pragma unroll
@@ -555,6 +610,9 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
         const int i = i0 + 16 * cb + chl;
         const i32x4 ors = w4_uniform(a.out_unit16 ? w4_rsrc(obase + (size_t)n * a.I * a.Ho * a.Wo, (unsigned)a.I * oplane) : pair_rsrc(obase, cb, qq));
         const unsigned choff = a.out_unit16 ? (i < a.I ? (unsigned)i * 64u : 0x40000000u) : 0u;      // (+ 0x80000000 of a dropped pixel: still out of range)
+        i32x4 prs = ors;
+        if constexpr (POOL) prs = w4_uniform(pair_rsrc(a.pooled, cb, qq, pplane));
+        float ye[4];                 // POOL: the even row above, kept until its odd partner arrives
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float y[4];
@@ -576,6 +634,20 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
           } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c) savfi_raw_buffer_store_x1(y[c], ors, (int)(ooff[r][c] + choff), 0, 0);
+          }
+          if constexpr (POOL) {
+            if (r % 2 == 0) {
+#pragma unroll
+              for (int c = 0; c < 4; ++c) ye[c] = y[c];
+            } else {
+              const float p0 = (((ye[0] + ye[1]) + y[0]) + y[1]) / 4.f, p1 = (((ye[2] + ye[3]) + y[2]) + y[3]) / 4.f;
+              if constexpr (VECW == 4) {
+                savfi_raw_buffer_store_x2((f32x2){p0, p1}, prs, (int)poff[r >> 1][0], 0, 0);
+              } else {
+                savfi_raw_buffer_store_x1(p0, prs, (int)poff[r >> 1][0], 0, 0);
+                savfi_raw_buffer_store_x1(p1, prs, (int)poff[r >> 1][1], 0, 0);
+              }
+            }
           }
         }
       }

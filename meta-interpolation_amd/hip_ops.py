@@ -4,6 +4,7 @@ Every function here launches a hand-written gfx950 kernel through the C ABI (inc
 on torch's current stream.  Device tensors only -- there is no CPU or eager-PyTorch fallback.
 """
 import collections
+import contextlib
 import functools
 import ctypes
 import os
@@ -145,6 +146,33 @@ class _AvgPool2x2Adjoint(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gg):
         return _AvgPool2x2.apply(gg.contiguous()), None
+
+
+def _avgpool2x2_fwd_launch(x):
+    """savfi_avgpool2x2_fwd_f32 on a contiguous device map, no autograd"""
+    N, C, H, W = x.shape
+    out = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
+    lib = _hip.lib()
+    _hip.launch("avgpool2x2_fwd", lambda: _hip.check(lib.savfi_avgpool2x2_fwd_f32(
+        x.data_ptr(), out.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_fwd_f32"),
+        nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
+    return out
+
+
+def _avgpool2x2_skip_adjoint(g_pool, g_skip, x, in_slope):
+    """gin = (pool^T(g_pool) + g_skip) * (x > 0 ? 1 : in_slope): the one backward pass of "pool AND keep" (savfi_avgpool2x2_bwd_fused_f32);
+    either cotangent may be None, in_slope None = no activation derivative"""
+    N, C, H, W = x.shape
+    g_pool = None if g_pool is None else g_pool.contiguous()
+    g_skip = None if g_skip is None else g_skip.contiguous()
+    gin = torch.empty_like(x)
+    lib = _hip.lib()
+    _hip.launch("avgpool2x2_bwd", lambda: _hip.check(lib.savfi_avgpool2x2_bwd_fused_f32(
+        None if g_pool is None else g_pool.data_ptr(), None if g_skip is None else g_skip.data_ptr(),
+        None if in_slope is None else x.data_ptr(), 1.0 if in_slope is None else float(in_slope), gin.data_ptr(),
+        N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_bwd_fused_f32"),
+        nbytes=4 * N * C * (H * W * (2 + (g_skip is not None)) + (H // 2) * (W // 2)))
+    return gin
 
 
 class _AvgPool2x2AndSkip(torch.autograd.Function):
@@ -1334,6 +1362,25 @@ def wino4_workgroups(N, Ci, Co, H, W, pad, mode=0):
     return max(n, 0)
 
 
+def wino4_launched_workgroups(N, Ci, Co, H, W, pad, mode=0):
+    """The grid an F(4x4) launch of this call really has: ceil(tiles / 32) workgroups per sample, split and channel block (flat tile
+    lists) -- routing keeps counting tile blocks, wino4_workgroups.  Not cached: it follows wino4_block_decode."""
+    n = int(_hip.lib().savfi_conv3x3_f4_launched_workgroups(int(N), int(Ci), int(Co), int(H), int(W), int(pad), int(mode)))
+    return max(n, 0)
+
+
+@contextlib.contextmanager
+def wino4_block_decode(on=True):
+    """Test hook: inside the block, F(4x4) launches decode their tiles by 2^(5-s) x 2^s blocks (the grid wino4_workgroups counts) instead of
+    flat tile lists.  Same results bit for bit; the previous setting comes back on exit."""
+    prev = ctypes.c_int(0)
+    _hip.check(_hip.lib().savfi_conv3x3_debug_f4_block_decode(1 if on else 0, ctypes.byref(prev)), "savfi_conv3x3_debug_f4_block_decode")
+    try:
+        yield
+    finally:
+        _hip.check(_hip.lib().savfi_conv3x3_debug_f4_block_decode(prev.value, None), "savfi_conv3x3_debug_f4_block_decode")
+
+
 def _layer(x_shape, w_shape, stride, padding, dilation, groups=1):
     """(N, Ci, Co, H, W, K, pad) of a layer with a _conv_geometry on [N,C,H,W] maps, else None: what the threshold rules below take."""
     geo = _conv_geometry(w_shape, stride, padding, dilation, groups)
@@ -1556,7 +1603,7 @@ def _aten_conv_backward(gz, x, w, stride, padding, dilation, groups, T, need_x, 
     return (torch.stack([p[0] for p in per], 1).view(N, Ci, H, W) if need_x else None), (torch.stack([p[1] for p in per], 0) if need_w else None)
 
 
-def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct, cache, reflect, in_slope, defer, out_unit16, T):
+def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct, cache, reflect, in_slope, defer, out_unit16, T, pool=False):
     """The forward of both fused convolutions.  T = None: shared weights w [Co,Ci,K,K], b [Co] (_ConvBiasAct: `groups`, the module-owned
     filter `cache`, the mirrored border `reflect`); else per-task weights w [T,Co,Ci,K,K], b [T,Co], sample s on task s % T
     (_ConvBiasActTasks: `out_unit16`).  The route is decided here, once, and kept on ctx for the backward."""
@@ -1583,7 +1630,10 @@ def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct
     elif route.fwd in ('wino', 'wino2'):
         # both filter transforms of this layer in one launch: the data gradient of the same step will want the other one
         u_fwd, ctx.u_bwd = filter_lookup(route.fwd, w, True, need_x and route.dgrad == route.fwd, cache)
-        z = conv3x3_tasks_pre(x, u_fwd, T or 1, Ci, Co, b, 0, slope, pad, out_unit16=bool(out_unit16), f2=route.fwd == 'wino2')
+        if pool:          # the 2 x 2 average of z from the kernel's output stage where the launch has one for it, else from the pooling kernel
+            z, pooled = conv3x3_tasks_pre_pool(x, u_fwd, T or 1, Ci, Co, b, slope, pad, f2=route.fwd == 'wino2')
+        else:
+            z = conv3x3_tasks_pre(x, u_fwd, T or 1, Ci, Co, b, 0, slope, pad, out_unit16=bool(out_unit16), f2=route.fwd == 'wino2')
     else:
         z = _aten_conv(x, w, stride, padding, dilation, groups, T)
         if b is not None or slope != 1.0:
@@ -1601,6 +1651,8 @@ def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct
     ctx.save_for_backward(x, w, z)
     if out_unit16:
         tag_layout(z, UNIT16)           # the tensor's shape does not say how its memory is laid out: its consumer checks the tag
+    if pool:
+        return z, (pooled if route.fwd in ('wino', 'wino2') else _avgpool2x2_fwd_launch(z))
     return z
 
 
@@ -2112,6 +2164,33 @@ def conv3x3_tasks_pre(x, u, T, Ci, Co, bias=None, mode=0, slope=1.0, pad=1, mask
     return out
 
 
+def conv3x3_tasks_pre_pool(x, u, T, Ci, Co, bias=None, slope=1.0, pad=1, f2=False):
+    """(y, avg_pool2x2(y)) of conv3x3_tasks_pre's forward (savfi_conv3x3_tasks_pre_pool_f32): the pooled map comes from the convolution's
+    output stage where the launch has one for it (F(4x4), an even unsplit output) and from savfi_avgpool2x2_fwd_f32 on y otherwise --
+    the same values bit for bit."""
+    x = x.contiguous()
+    _hip.require_cuda(x, u)
+    fbit = 2 if f2 else 0
+    N, _, H, W = x.shape
+    assert N % T == 0 and x.shape[1] == Ci, (x.shape, T, Ci, Co)
+    shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 0)
+    assert shape[2] >= 2 and shape[3] >= 2, shape
+    lib = _hip.lib()
+    nws = _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, T, Ci, Co, H, W, int(pad), fbit)
+    ws = torch.empty(nws, dtype=x.dtype, device=x.device) if nws else None
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    pooled = torch.empty(shape[:2] + (shape[2] // 2, shape[3] // 2), dtype=x.dtype, device=x.device)
+    did = ctypes.c_int(0)
+    name = "conv3x3_fwd" if f2 else _conv3x3_name(Ci, Co, "fwd")
+    _hip.launch(name, lambda: _hip.check(lib.savfi_conv3x3_tasks_pre_pool_f32(
+        x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), pooled.data_ptr(),
+        None if ws is None else ws.data_ptr(), N, T, Ci, Co, H, W, int(pad), fbit, float(slope), ctypes.byref(did), _hip.current_stream()),
+        "savfi_conv3x3_tasks_pre_pool_f32"), flops=flops)
+    if not did.value:
+        pooled = _avgpool2x2_fwd_launch(out)
+    return out, pooled
+
+
 def _conv3x3_dgrad_masked(gy, u, T, Ci, Co, pad, mask, mask_slope, fbit=0):
     N, _, H, W = gy.shape
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 1)
@@ -2399,6 +2478,52 @@ class _ConvBiasActTasks(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         return _conv_backward(ctx, gy) + (None,) * 8
+
+
+class _ConvBiasActTasksPool(torch.autograd.Function):
+    """(y, avg_pool2x2(y)) with y = act(conv2d(x[s], w[s % T]) + b[s % T]): an encoder block's last layer, whose activated output feeds the
+    pooling and a skip connection.  Forward: the F(4x4) kernel's output stage stores the pooled map from the tile it holds in registers
+    (csrc/winograd4.h, POOL; savfi_avgpool2x2_fwd_f32's expression and order, so the same bits) -- the pooling kernel read the whole map
+    back for it; launches without that epilogue run the pooling kernel as before.  backward(g_skip, g_pool): _AvgPool2x2AndSkip's one
+    pass, gz = (pool^T(g_pool) + g_skip) * act'(y), then _ConvBiasActTasks's backward on gz as the cotangent of a layer that deferred its
+    activation derivative -- the kernels, in the order, of conv_bias_act_tasks(defer=True) -> avg_pool2x2_and_skip.  First-order only."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride, padding, dilation, slope, direct=False, in_slope=None):
+        ctx.set_materialize_grads(False)
+        return _conv_forward(ctx, x, w, b, stride, padding, dilation, 1, slope, direct, None, False, in_slope, True, 0, w.shape[0], pool=True)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_skip, g_pool):
+        if g_skip is None and g_pool is None:
+            return (None,) * 9
+        y = ctx.saved_tensors[2]
+        slope = ctx.conf[4]
+        gz = _avgpool2x2_skip_adjoint(g_pool, g_skip, y, None if slope == 1.0 else slope)
+        return _conv_backward(ctx, gz) + (None,) * 6
+
+
+def conv_bias_act_tasks_pool(x, weight, bias, stride=1, padding=0, dilation=1, slope=0.0, direct=False, in_slope=None):
+    """(y, avg_pool2x2(y)) of conv_bias_act_tasks -- see _ConvBiasActTasksPool.  y's activation derivative is applied by this op's own
+    backward: its consumers see an ordinary tensor (nothing is deferred to them).  Maps of at least 2 x 2 pixels."""
+    return _ConvBiasActTasksPool.apply(x, weight, bias, stride, padding, dilation, float(slope), bool(direct),
+                                       None if in_slope is None else float(in_slope))
+
+
+def conv_pools_in_epilogue(x, weight, stride, padding, dilation):
+    """Does conv_bias_act_tasks's forward of this per-task layer run on the F(4x4) kernel with an output stage that can pool (an even,
+    unsplit output of at least 2 rows)?  Where MetaNetwork's encoder uses conv_bias_act_tasks_pool."""
+    if not (_f32_map(x) and weight.dim() == 5):
+        return False
+    route = conv_route(x.shape, weight.shape, stride, padding, dilation)
+    if route.fwd != 'wino':
+        return False
+    N, Ci, H, W = x.shape
+    Ho, Wo = H + 2 * route.pad - 2, W + 2 * route.pad - 2
+    if Ho < 2 or Wo < 2 or Wo % 2 != 0 or wino4_workgroups(N, Ci, weight.shape[1], H, W, route.pad, 0) <= 0:
+        return False
+    return _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, weight.shape[0], Ci, weight.shape[1], H, W, route.pad, 0) == 0
 
 
 def conv_bias_act_tasks(x, weight, bias, stride=1, padding=0, dilation=1, slope=0.0, direct=False, in_slope=None, defer=False,

@@ -203,7 +203,10 @@ class MetaConv2dLayer(nn.Module):
         the image (MetaConvNorm; the caller has checked hip_ops.convk_reflect_eligible).
         conv -> act -> conv chains (MetaSequential): `chain` = {'want_defer': True} asks this layer to leave its activation derivative
         to its single consumer -- honoured on the fused paths only, which then set chain['deferred'] --; `in_slope` = x is the
-        activated output of a producer that did: its derivative is folded into this layer's data gradient."""
+        activated output of a producer that did: its derivative is folded into this layer's data gradient.
+        chain['want_pool'] (with want_defer): the caller average-pools the result 2 x 2 and keeps it as a skip connection; where the layer
+        runs on the kernel whose output stage pools (hip_ops.conv_pools_in_epilogue) it sets chain['pooled'] to the pooled map and defers
+        NOTHING -- hip_ops.conv_bias_act_tasks_pool's backward applies the derivative itself."""
         padding = self.padding if padding is None else padding
         want_defer = bool(chain and chain.get('want_defer')) and act_slope is not None and not reflect
 
@@ -225,6 +228,10 @@ class MetaConv2dLayer(nn.Module):
             if x.is_cuda and fuse_conv_act() and self.groups == 1 and (
                     act_slope is not None or bias is None or hip_ops.conv3x3_tasks_eligible(x, weight, self.stride, padding, self.dilation_rate)
                     or hip_ops.convk_eligible(x, weight, self.stride, padding, self.dilation_rate, 1, direct)):
+                if want_defer and chain.get('want_pool') and hip_ops.conv_pools_in_epilogue(x, weight, self.stride, padding, self.dilation_rate):
+                    out, chain['pooled'] = hip_ops.conv_bias_act_tasks_pool(x, weight, bias, self.stride, padding, self.dilation_rate,
+                                                                            act_slope, direct, in_slope)
+                    return out
                 return fused(hip_ops.conv_bias_act_tasks, x, weight, bias, self.stride, padding, self.dilation_rate,
                              1.0 if act_slope is None else act_slope, direct)
             assert self.groups == 1, "lockstep tasks on a grouped convolution"
@@ -313,13 +320,16 @@ class MetaSequential(nn.Sequential):
     def is_meta_layer(self, module):
         return isinstance(module, _META_TYPES)
 
-    def forward(self, input, params=None, in_slope=None, defer_last=False):
+    def forward(self, input, params=None, in_slope=None, defer_last=False, pool_last=False):
         """in_slope: `input` is the activated output of a convolution that left its activation derivative to this Sequential's first
         module (a MetaConv2dLayer or an Upsample2x).  defer_last: the caller promises that the result has exactly one consumer that can
         take over the LAST conv + activation pair's derivative (an Upsample2x; a Sequential called with in_slope): returns (result,
-        slope or None) instead of the result."""
+        slope or None) instead of the result.  pool_last (with defer_last): that consumer is "average-pool 2 x 2 and keep as a skip
+        connection"; returns (result, slope or None, pooled or None) -- pooled is the pooled result where the last convolution's kernel
+        made it (MetaConv2dLayer.forward, want_pool; the slope is then None), else None and the caller pools."""
         pv = as_view(params)
         mods = list(self)
+        pooled = None
         ind = 0                         # in_slope: the previous conv left its activation derivative to the next module (see below)
         while ind < len(mods):
             module = mods[ind]
@@ -340,6 +350,8 @@ class MetaSequential(nn.Sequential):
                 if "act_slope" in kw and takes_over and input.is_cuda \
                         and fuse_conv_chain() and fuse_conv_act() and not hip_ops.double_backward() and torch.is_grad_enabled():
                     chain = {"want_defer": True}
+                    if pool_last and defer_last and ind + 2 >= len(mods):
+                        chain["want_pool"] = True
                     kw["chain"] = chain
             elif isinstance(module, hip_ops.Upsample2x):
                 if in_slope is not None:
@@ -351,7 +363,11 @@ class MetaSequential(nn.Sequential):
             else:
                 input = module(input, **kw)
             in_slope = kw["act_slope"] if (chain is not None and chain.get("deferred")) else None
+            pooled = chain.get("pooled") if chain is not None else None
             ind += step
+        if pool_last:
+            assert defer_last
+            return input, in_slope, pooled
         if defer_last:
             return input, in_slope
         assert in_slope is None

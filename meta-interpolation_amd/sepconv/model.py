@@ -36,6 +36,7 @@ TAPS_UNIT16 = True        # A/B (module attributes, no environment variable): Fa
 GRADS_UNIT16 = True
 FRAME_CACHE = True        # False: pads / concatenation of the frame pair once per forward
 CROP_EXACT = False        # True: the Subnets' window without the alignment slack
+POOL_EPILOGUE = True      # False: every encoder block's pooling as its own kernel (hip_ops.avg_pool2x2_and_skip)
 
 FILTER_TAPS = 51
 HALF = FILTER_TAPS // 2  # 25
@@ -115,10 +116,13 @@ class MetaNetwork(nn.Module):
         for i, (name, _, _) in enumerate(_ENCODER, start=1):
             # the block's activated output feeds the pooling and a skip connection: one op with one element-wise pass in backward (the
             # pooling's adjoint + the sum of the two cotangents + the block's last ReLU derivative, which the block leaves to it)
-            x, slope = getattr(self, name)(x, fast(name), defer_last=True)
+            # (where the block's last layer runs on the F(4x4) kernel, its output stage has stored the pooled map already: POOL_EPILOGUE)
             if x.is_cuda:
-                x, skip = hip_ops.avg_pool2x2_and_skip(x, slope)
+                res = getattr(self, name)(x, fast(name), defer_last=True, pool_last=POOL_EPILOGUE)
+                x, slope, pooled = res if POOL_EPILOGUE else res + (None,)
+                x, skip = (pooled, x) if pooled is not None else hip_ops.avg_pool2x2_and_skip(x, slope)
             else:
+                x, slope = getattr(self, name)(x, fast(name), defer_last=True)
                 assert slope is None
                 x, skip = getattr(self, "modulePool%d" % i)(x), x
             skips.append(skip)
