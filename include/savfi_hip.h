@@ -39,6 +39,7 @@
  *   savfi_frames_u8_to_f32     HWC uint8 frames -> normalised fp32 NCHW  data/vimeo_septuplet.py:68-80, data/video.py:44-51
  *   savfi_frames_f32_to_u8     unit-range fp32 NCHW -> quantised uint8 NHWC (what save_image writes)   utils.py:171-172, :276-285
  *   savfi_filterinterp_fwd/bwd_f32   DAIN's adaptive warping layer (per-pixel 4x4 filter at the flow-displaced position)
+ *   savfi_filterinterp_fwd_slice_f32 the same forward written into a channel slice of a wider tensor (MetaDAIN's rectify input)
  *                                                                     dain/my_package/FilterInterpolation/filterinterpolation_cuda_kernel.cu:29-460
  *   savfi_depthflowproj_fwd/bwd_f32  DAIN's depth-aware flow projection (scatter, average, hole fill)
  *                                                                     dain/my_package/DepthFlowProjection/depthflowprojection_cuda_kernel.cu:29-341
@@ -77,7 +78,7 @@ extern "C" {
  * savfi_pwcwarp_fwd_f32; then, for DAIN's frozen front and rectify net, savfi_bn_stats_scratch_floats, savfi_bn_stats_f32,
  * savfi_bn_apply_relu_f32, savfi_bn_running_update_f32, savfi_maxpool2x2_f32, savfi_upnearest2x_add_f32, savfi_add_relu_f32,
  * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32; then savfi_conv3x3_f4_launched_workgroups, savfi_conv3x3_debug_f4_block_decode,
- * savfi_conv3x3_tasks_pre_pool_f32. */
+ * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -662,6 +663,12 @@ int savfi_filterinterp_fwd_f32(const float* in, const float* flow, const float* 
 int savfi_filterinterp_bwd_f32(const float* in, const float* flow, const float* filt, const float* gout, float* g_in /*nullable*/,
                                float* g_flow /*nullable*/, float* g_filt /*nullable*/, int B, int C, int H, int W, int filter_size,
                                void* stream);
+/* The forward into a channel slice, added under ABI 24: out is [B,C_total,H,W] and the call writes out[b][c_off + c][y][x], c < C, with
+ * the arithmetic of savfi_filterinterp_fwd_f32 in its order (the same bits, the pass-through of an invalid pixel included); every
+ * other channel of `out` is left as it was.  One launch, no memset, no atomics: capturable.  c_off < 0 or c_off + C > C_total:
+ * SAVFI_E_SHAPE; the limits above hold for C and for C_total (B*C_total*H*W < 2^40, the OUTPUT's elements). */
+int savfi_filterinterp_fwd_slice_f32(const float* in, const float* flow, const float* filt, float* out, int B, int C, int H, int W,
+                                     int filter_size, int C_total, int c_off, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * DAIN's depth-aware flow projection (csrc/dainwarp.hip; DepthFlowProjection/depthflowprojection_cuda_kernel.cu:29-341), ABI 24.

@@ -140,6 +140,7 @@ _PROTOTYPES = {
     "savfi_bias_act_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P],
     "savfi_filterinterp_fwd_f32": [_P, _P, _P, _P] + [c_int] * 5 + [_P],
     "savfi_filterinterp_bwd_f32": [_P] * 7 + [c_int] * 5 + [_P],
+    "savfi_filterinterp_fwd_slice_f32": [_P, _P, _P, _P] + [c_int] * 7 + [_P],
     "savfi_depthflowproj_scratch_bytes": [c_int, c_int, c_int],
     "savfi_depthflowproj_fwd_f32": [_P] * 5 + [c_int] * 4 + [_P],
     "savfi_depthflowproj_bwd_f32": [_P] * 7 + [c_int] * 3 + [_P],

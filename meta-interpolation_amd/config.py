@@ -14,6 +14,8 @@ Additions for the MI355X build (all optional, all default to the reference behav
   --task_batch T               adapt up to T tasks of a meta-batch in LOCKSTEP: one launch per layer for all of them, per-task fast
                                weights (default 8; first order -- second order, L2F on partly routed plugins and T <= 1 take the
                                reference's sequential task loop)
+  --dain_task_modes {0,1}      --model dain: 1 lets the MetaDAIN plugin adapt its tasks in lockstep (--task_batch) and from captured hipGraphs
+                               (--graph_inner_loop) on fronts evaluated once per group; default 0: the sequential eager task loop
   --synthetic                  feed seeded synthetic septuplets instead of reading a dataset
 """
 import argparse
@@ -49,6 +51,7 @@ _FLAGS = {
     'MI355X': [
         ('fuse_support_pairs', int, 1), ('fuse_conv_act', int, 1), ('graph_inner_loop', int, -1), ('sepconv_window', int, 1),
         ('task_streams', int, -1), ('wgrad_overlap', int, 0), ('task_batch', int, 8), ('lazy_logging', int, 1),
+        ('dain_task_modes', int, 0),
         ('synthetic', 'flag', False),
     ],
 }

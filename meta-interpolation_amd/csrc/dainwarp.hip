@@ -60,20 +60,16 @@ __device__ __forceinline__ WarpGeom warp_geom(float fx, float fy, int w_i, int h
 // tap (j, i) of the window belongs to quadrant 2 * (j >= 2) + (i >= 2): rows 0-1 "top" (filter_j <= int(y2)), columns 0-1 "left"
 __device__ __forceinline__ constexpr int quad_of(int k) { return 2 * ((k >> 2) >> 1) + ((k & 3) >> 1); }
 
-// grid: (pixel blocks, channel chunks, B)
-__global__ __launch_bounds__(NT) void filterinterp_fwd(const float* __restrict__ in, const float* __restrict__ flow,
-                                                       const float* __restrict__ filt, float* __restrict__ out, int C, int H, int W,
-                                                       int cpc) {
+// One pixel of one channel chunk, shared by both forwards: `dst` is the output element of channel c0 at pixel p, its channels one
+// plane apart (whatever tensor they lie in).
+__device__ __forceinline__ void filterinterp_pixel(const float* __restrict__ in, const float* __restrict__ flow,
+                                                   const float* __restrict__ filt, float* __restrict__ dst, int b, int c0, int c1, int p,
+                                                   int C, int H, int W) {
   const int plane = H * W;                                  // < 2^31 (entry check)
-  const int p = blockIdx.x * NT + threadIdx.x;
-  if (p >= plane) return;
-  const int b = blockIdx.z;
-  const int c0 = blockIdx.y * cpc, c1 = min(C, c0 + cpc);
   const int h_i = p / W, w_i = p - h_i * W;
   const float* fl = flow + (size_t)b * 2 * plane + p;
   const WarpGeom g = warp_geom(fl[0], fl[plane], w_i, h_i, W, H);
   const float* src = in + ((size_t)b * C + c0) * plane;
-  float* dst = out + ((size_t)b * C + c0) * plane + p;
   if (!g.valid) {                                           // .cu:151-156: the input passes through
     for (int c = c0; c < c1; ++c, src += plane, dst += plane) *dst = src[p];
     return;
@@ -92,6 +88,31 @@ __global__ __launch_bounds__(NT) void filterinterp_fwd(const float* __restrict__
     for (int k = 0; k < 16; ++k) q[quad_of(k)] = fmaf(wt[k], src[idx[k]], q[quad_of(k)]);
     *dst = (q[0] + q[1]) + (q[2] + q[3]);
   }
+}
+
+// grid: (pixel blocks, channel chunks, B)
+__global__ __launch_bounds__(NT) void filterinterp_fwd(const float* __restrict__ in, const float* __restrict__ flow,
+                                                       const float* __restrict__ filt, float* __restrict__ out, int C, int H, int W,
+                                                       int cpc) {
+  const int plane = H * W;
+  const int p = blockIdx.x * NT + threadIdx.x;
+  if (p >= plane) return;
+  const int b = blockIdx.z;
+  const int c0 = blockIdx.y * cpc, c1 = min(C, c0 + cpc);
+  filterinterp_pixel(in, flow, filt, out + ((size_t)b * C + c0) * plane + p, b, c0, c1, p, C, H, W);
+}
+
+// The same into channels [c_off, c_off + C) of out [B, C_total, H, W]: scalar stores one plane apart, as above -- a slice base
+// c_off * H * W has no alignment beyond a float's -- and no other channel of `out` is touched.  Same grid.
+__global__ __launch_bounds__(NT) void filterinterp_fwd_slice(const float* __restrict__ in, const float* __restrict__ flow,
+                                                             const float* __restrict__ filt, float* __restrict__ out, int C, int H,
+                                                             int W, int cpc, int C_total, int c_off) {
+  const int plane = H * W;
+  const int p = blockIdx.x * NT + threadIdx.x;
+  if (p >= plane) return;
+  const int b = blockIdx.z;
+  const int c0 = blockIdx.y * cpc, c1 = min(C, c0 + cpc);
+  filterinterp_pixel(in, flow, filt, out + ((size_t)b * C_total + c_off + c0) * plane + p, b, c0, c1, p, C, H, W);
 }
 
 __global__ __launch_bounds__(NT) void zero_f32(float* __restrict__ p, size_t n) {
@@ -384,18 +405,38 @@ int ceil_log2(int64_t v) {
 
 }  // namespace
 
+// channel chunks: enough workgroups for 256 CUs x 8 on a small map, at least 4 channels a thread to amortise the 16 tap products
+static void warp_chunks(int B, int C, int pb, int* chunks_out, int* cpc_out) {
+  int chunks = savfi_cdiv(2048, (int64_t)pb * B);
+  chunks = chunks < 1 ? 1 : chunks;
+  int cpc = savfi_cdiv(C, chunks);
+  if (cpc < 4) cpc = C < 4 ? C : 4;
+  *chunks_out = savfi_cdiv(C, cpc);
+  *cpc_out = cpc;
+}
+
 extern "C" int savfi_filterinterp_fwd_f32(const float* in, const float* flow, const float* filt, float* out, int B, int C, int H, int W,
                                           int filter_size, void* stream) {
   if (!in || !flow || !filt || !out) return SAVFI_E_NULL;
   if (int e = warp_check(B, C, H, W, filter_size)) return e;
   const int pb = savfi_cdiv((int64_t)H * W, NT);
-  // channel chunks: enough workgroups for 256 CUs x 8 on a small map, at least 4 channels a thread to amortise the 16 tap products
-  int chunks = savfi_cdiv(2048, (int64_t)pb * B);
-  chunks = chunks < 1 ? 1 : chunks;
-  int cpc = savfi_cdiv(C, chunks);
-  if (cpc < 4) cpc = C < 4 ? C : 4;
-  chunks = savfi_cdiv(C, cpc);
+  int chunks, cpc;
+  warp_chunks(B, C, pb, &chunks, &cpc);
   hipLaunchKernelGGL(filterinterp_fwd, dim3(pb, chunks, B), dim3(NT), 0, (hipStream_t)stream, in, flow, filt, out, C, H, W, cpc);
+  return savfi_launch_status();
+}
+
+extern "C" int savfi_filterinterp_fwd_slice_f32(const float* in, const float* flow, const float* filt, float* out, int B, int C, int H,
+                                                int W, int filter_size, int C_total, int c_off, void* stream) {
+  if (!in || !flow || !filt || !out) return SAVFI_E_NULL;
+  if (C_total <= 0 || c_off < 0 || (int64_t)c_off + C > C_total) return SAVFI_E_SHAPE;
+  if (int e = warp_check(B, C, H, W, filter_size)) return e;
+  if (int e = warp_check(B, C_total, H, W, filter_size)) return e;      // the OUTPUT's element count
+  const int pb = savfi_cdiv((int64_t)H * W, NT);
+  int chunks, cpc;
+  warp_chunks(B, C, pb, &chunks, &cpc);
+  hipLaunchKernelGGL(filterinterp_fwd_slice, dim3(pb, chunks, B), dim3(NT), 0, (hipStream_t)stream, in, flow, filt, out, C, H, W, cpc,
+                     C_total, c_off);
   return savfi_launch_status();
 }
 

@@ -6,6 +6,9 @@ the context net twice, the filter net, two projections and four warps -- is a fu
 ``front(frame0, frame1)``, run under no_grad, and ``forward(frame0, frame1, params, front=...)`` is the rectify net on a given front:
 a caller that adapts on a triplet evaluates its front once and passes it to every pass over that triplet.  ``forward`` computes the
 front itself when none is given (the reference's structure; ``reuse_front = False`` tells the system to do that on every pass).
+``front(..., out=alloc_front(...))`` builds the front in place at fixed addresses (the four warps write their channel slices of the rectify
+input), and ``forward(..., update_stats=False)`` with ``replay_running_stats`` lets a caller run several tasks' passes on shared fronts
+and still move the running statistics in the sequential loop's order: what the lockstep and hipGraph paths (--dain_task_modes 1) use.
 
 Kept from the reference: the sub-networks' names (dain_base.pth loads by name), the order of constructing and initialising them, the stack
 logic of the filter net, div_flow = 20 and the bilinear x4 of the flows, the reflection padding to multiples of 64 and its inverse.
@@ -52,7 +55,8 @@ class Front:
 
 
 class MetaDAIN(torch.nn.Module):
-    graph_capture = False     # this plugin takes the sequential eager task body (graph_inner_loop.supported)
+    graph_capture = False     # by default this plugin takes the sequential eager task body (graph_inner_loop.supported); --dain_task_modes 1
+                              # sets graph_capture and lockstep_tasks on the system's INSTANCE
     reuse_front = True        # A/B (bench, tests): False = the system recomputes the front on every pass, as the reference does
 
     def __init__(self, channel=3, filter_size=4, timestep=0.5, training=True, resume=False):
@@ -117,15 +121,38 @@ class MetaDAIN(torch.nn.Module):
         left, right, top, bottom = padding
         return x[..., top:x.shape[-2] - bottom, left:x.shape[-1] - right]
 
+    # channels of rectify_input: cur_output, ref0, ref2, the two offsets, the two filter sets, the two warped contexts
+    RECTIFY_CHANNELS = 437
+    _SLICES = {'cur_output': 0, 'ref0': 3, 'ref2': 6, 'offset0': 9, 'offset1': 11, 'filter0': 13, 'filter1': 29, 'ctx0': 45, 'ctx2': 241}
+
+    @classmethod
+    def alloc_front(cls, B, H, W, device):
+        """A Front for B pairs of H x W frames whose ``rectify_input`` and ``cur_output`` are allocated (zeroed) for the padded size:
+        what ``front(..., out=)`` fills in place, call after call, at fixed addresses (graph_inner_loop.py)."""
+        padding = cls.paddings(H, W)
+        Hp, Wp = H + padding[2] + padding[3], W + padding[0] + padding[1]
+        return Front(torch.zeros(B, cls.RECTIFY_CHANNELS, Hp, Wp, device=device), torch.zeros(B, 3, Hp, Wp, device=device), padding, None)
+
     @torch.no_grad()
-    def front(self, frame0, frame1, keep_parts=False):
+    def front(self, frame0, frame1, keep_parts=False, out=None):
         """Everything of the reference's forward that does not depend on ``params``, for B frame pairs [B,3,H,W] at once; each pair is
-        one BatchNorm group of the depth net.  Returns a Front."""
+        one BatchNorm group of the depth net.  Returns a Front.
+
+        ``out``: a Front of alloc_front(B, H, W, device) to fill in place: the four warps write their channel slices of its
+        ``rectify_input`` themselves, the other 39 channels are copied in, ``cur_output`` is written, ``bn_stats`` (and ``parts``) are
+        replaced -- the same bits as without ``out``, no 437-channel temporary, and ``out`` is what is returned."""
         _hip.require_cuda(frame0.contiguous(), frame1.contiguous())
         assert frame0.shape == frame1.shape and frame0.dim() == 4
         B = frame0.shape[0]
-        self.front_evaluations += B
         padding = self.paddings(frame0.shape[2], frame0.shape[3])
+        if out is not None:
+            Hp, Wp = frame0.shape[2] + padding[2] + padding[3], frame0.shape[3] + padding[0] + padding[1]
+            if (tuple(out.rectify_input.shape) != (B, self.RECTIFY_CHANNELS, Hp, Wp) or tuple(out.cur_output.shape) != (B, 3, Hp, Wp)
+                    or tuple(out.padding) != tuple(padding)):
+                raise ValueError("front(out=): %s / %s is no Front of alloc_front for %d pairs of %d x %d frames"
+                                 % (tuple(out.rectify_input.shape), tuple(out.cur_output.shape), B, frame0.shape[2], frame0.shape[3]))
+            _hip.require_cuda(out.rectify_input, out.cur_output)
+        self.front_evaluations += B
         if any(padding):
             pad = nn.ReflectionPad2d(list(padding))
             frame0, frame1 = pad(frame0), pad(frame1)
@@ -162,25 +189,63 @@ class MetaDAIN(torch.nn.Module):
         cur_offset_outputs = [self.FlowProject(flows[0], depth_inv[0]), self.FlowProject(flows[1], depth_inv[1])]
 
         cur_offset_output = [cur_offset_outputs[0][0], cur_offset_outputs[1][0]]
+        parts = None
+        if keep_parts:
+            parts = {'input0': cur_input_0, 'input2': cur_input_2, 'log_depth': log_depth, 'ctx': ctx, 'filter_trunk': temp,
+                     'filters': cur_filter_output, 'depth_inv': depth_inv, 'flows': [flows[0][0], flows[1][0]],
+                     'offsets': cur_offset_output}
+        if out is not None:
+            return self._front_into(out, cur_input_0, cur_input_2, cur_ctx_output, cur_offset_output, cur_filter_output, bn_stats, parts)
         ctx0, ctx2 = self.FilterInterpolate_ctx(cur_ctx_output[0], cur_ctx_output[1], cur_offset_output, cur_filter_output)
         cur_output, ref0, ref2 = self.FilterInterpolate(cur_input_0, cur_input_2, cur_offset_output, cur_filter_output,
                                                         self.filter_size ** 2)
         rectify_input = torch.cat((cur_output, ref0, ref2, cur_offset_output[0], cur_offset_output[1],
                                    cur_filter_output[0], cur_filter_output[1], ctx0, ctx2), dim=1)
-        parts = None
         if keep_parts:
-            parts = {'input0': cur_input_0, 'input2': cur_input_2, 'log_depth': log_depth, 'ctx': ctx, 'filter_trunk': temp,
-                     'filters': cur_filter_output, 'depth_inv': depth_inv, 'flows': [flows[0][0], flows[1][0]],
-                     'offsets': cur_offset_output, 'ctx_warped': [ctx0, ctx2], 'refs': [ref0, ref2]}
+            parts.update({'ctx_warped': [ctx0, ctx2], 'refs': [ref0, ref2]})
         return Front(rectify_input, cur_output, padding, bn_stats, parts)
 
-    def forward(self, frame0, frame1, params=None, front=None, **kwargs):
+    def _front_into(self, out, input0, input2, ctx, offset, filt, bn_stats, parts):
+        """The tail of front() into ``out``: FilterInterpolate_ctx, FilterInterpolate and the concatenation, without the concatenation."""
+        ri, at = out.rectify_input, self._SLICES
+        for name, src in (('ctx0', ctx[0]), ('ctx2', ctx[1]), ('ref0', input0), ('ref2', input2)):
+            k = 0 if name in ('ctx0', 'ref0') else 1
+            hip_ops.filter_interpolation_into(ri, at[name], src, offset[k], filt[k])
+        ref0, ref2 = ri[:, at['ref0']:at['ref0'] + 3], ri[:, at['ref2']:at['ref2'] + 3]
+        torch.add(ref0 / 2.0, ref2 / 2.0, out=out.cur_output)         # FilterInterpolate's ref0_offset / 2.0 + ref2_offset / 2.0
+        for name, src in (('cur_output', out.cur_output), ('offset0', offset[0]), ('offset1', offset[1]), ('filter0', filt[0]),
+                          ('filter1', filt[1])):
+            ri[:, at[name]:at[name] + src.shape[1]].copy_(src)
+        if parts is not None:                                          # views of the slices
+            n = self.ctx_ch + 1
+            parts.update({'ctx_warped': [ri[:, at['ctx0']:at['ctx0'] + n], ri[:, at['ctx2']:at['ctx2'] + n]], 'refs': [ref0, ref2]})
+        out.bn_stats, out.parts = bn_stats, parts
+        return out
+
+    def replay_running_stats(self, support, target, tasks, passes):
+        """The depth net's running-statistics updates of the sequential task loop, for ``tasks`` tasks whose passes ran on shared fronts
+        with update_stats=False: ``support`` holds the 2 x tasks support pairs in sample-major order (pair j * tasks + t is support j of
+        task t), ``target`` the tasks target pairs; ``passes`` is one task's forwards in order, 's' = a support pass (its two pairs, a
+        then b), 't' = a target pass.  Task by task, as the reference's loop applies them.  Eager: never inside a captured graph."""
+        if not self.training or support.bn_stats is None:
+            return
+        for t in range(tasks):
+            for p in passes:
+                if p == 's':
+                    self.depthNet.update_running_stats(support.bn_stats, groups=[t, tasks + t])
+                else:
+                    self.depthNet.update_running_stats(target.bn_stats, groups=[t])
+
+    def forward(self, frame0, frame1, params=None, front=None, update_stats=True, **kwargs):
         """The rectified middle frame [B,3,H,W] of frame0, frame1 [B,3,H,W]; ``params``: fast weights of rectifyNet (names with or
-        without the 'rectifyNet.' prefix of the inner-loop dictionary); ``front``: front(frame0, frame1) when the caller has it.
-        In training mode the depth net's running statistics move as in one reference forward per pair."""
+        without the 'rectifyNet.' prefix of the inner-loop dictionary; stacked [T, ...] for T tasks in lockstep over a batch in
+        sample-major order); ``front``: front(frame0, frame1) when the caller has it.
+        In training mode the depth net's running statistics move as in one reference forward per pair, unless ``update_stats`` is
+        False: a caller that runs several tasks' passes on one front (lockstep, captured graphs) replays the updates in the
+        sequential loop's order afterwards (replay_running_stats)."""
         if front is None:
             front = self.front(frame0, frame1)
-        if self.training and front.bn_stats is not None:
+        if update_stats and self.training and front.bn_stats is not None:
             self.depthNet.update_running_stats(front.bn_stats)
         pv = as_view(params)
         if pv is not None and 'rectifyNet' in pv:

@@ -47,6 +47,8 @@ def supported(system, use_second_order):
         return False
     if not getattr(system.net, 'graph_capture', True):      # a plugin that has not opted in (dain): the sequential eager task body
         return False
+    if hasattr(system.net, 'front') and not system._shared_fronts():     # dain with reuse_front = False: a front per pass, eagerly
+        return False
     return (bool(getattr(a, 'graph_inner_loop', 0)) and system.device.type == 'cuda' and not use_second_order
             and hasattr(system.inner_loop_optimizer, 'lr_mode'))
 
@@ -72,6 +74,12 @@ class GraphedInnerLoop:
         T = self.T
         self.sup = [torch.zeros(2 * T, C, H, W, device=dev) for _ in range(3)]      # frame0 | target | frame1, pair batch
         self.tgt = [torch.zeros(T, C, H, W, device=dev) for _ in range(3)]
+        # a plugin with a frozen front (dain): static fronts, refilled eagerly before the replays of every call (run_tasks); the
+        # captured passes read them and leave the depth net's running statistics to the eager replay that follows
+        self.sup_kw, self.tgt_kw = {}, {}
+        if system._shared_fronts():
+            self.sup_kw = {'front': self.net.alloc_front(2 * T, H, W, dev), 'update_stats': False}
+            self.tgt_kw = {'front': self.net.alloc_front(T, H, W, dev), 'update_stats': False}
         stacked = (lambda p: torch.zeros_like(p)) if T == 1 else (lambda p: torch.zeros((T,) + tuple(p.shape), device=dev))
         self._like = stacked
         self.W0 = {k: stacked(self.theta[k]).requires_grad_() for k in self.routed}
@@ -101,7 +109,7 @@ class GraphedInnerLoop:
         dev = self.sys.device
         fast = {k: v.detach().clone().requires_grad_() for k, v in self.theta.items()}
         x = torch.zeros(1, C, H, W, device=dev)
-        out = _frame(self.net.forward(x, x, params=fast, backup_running_statistics=False, num_step=0))
+        out = _frame(self.net.forward(x, x, params=fast, backup_running_statistics=False, num_step=0, **self.sys._probe_kw(self.shape)))
         g = torch.autograd.grad(out.sum(), list(fast.values()), allow_unused=True)
         self.routed = [k for k, gi in zip(self.all_keys, g) if gi is not None]
         self.unrouted = [k for k, gi in zip(self.all_keys, g) if gi is None]
@@ -117,7 +125,8 @@ class GraphedInnerLoop:
             hip_ops.filters_after_update([W[k] for k in self.routed])
         model_utils.set_own_params_const(True)      # first-order support pass: non-routed parameters are constants
         try:
-            out = _frame(self.net.forward(self.sup[0], self.sup[2], params=W, backup_running_statistics=(t == 0), num_step=t))
+            out = _frame(self.net.forward(self.sup[0], self.sup[2], params=W, backup_running_statistics=(t == 0), num_step=t,
+                                          **self.sup_kw))
         finally:
             model_utils.set_own_params_const(False)
         if self.T == 1:
@@ -140,7 +149,7 @@ class GraphedInnerLoop:
         fused per-tensor mean."""
         model_utils.set_own_params_const(True)
         try:
-            out = _frame(self.net.forward(self.sup[0], self.sup[2], params=W, backup_running_statistics=True, num_step=0))
+            out = _frame(self.net.forward(self.sup[0], self.sup[2], params=W, backup_running_statistics=True, num_step=0, **self.sup_kw))
         finally:
             model_utils.set_own_params_const(False)
         loss = self.crit(out[0:1], self.sup[1][0:1])['total'] + self.crit(out[1:2], self.sup[1][1:2])['total']
@@ -151,10 +160,11 @@ class GraphedInnerLoop:
         crit = self.crit if self.T == 1 else self.crit.per_sample          # T > 1: every loss part is a [T] vector
         if not with_grad:
             with torch.no_grad():
-                pred = _frame(self.net.forward(self.tgt[0], self.tgt[2], params=W, backup_running_statistics=False, num_step=s))
+                pred = _frame(self.net.forward(self.tgt[0], self.tgt[2], params=W, backup_running_statistics=False, num_step=s,
+                                               **self.tgt_kw))
                 parts = crit(pred, self.tgt[1])
             return dict(pred=pred, parts={k: v.detach() for k, v in parts.items()})
-        pred = _frame(self.net.forward(self.tgt[0], self.tgt[2], params=W, backup_running_statistics=False, num_step=s))
+        pred = _frame(self.net.forward(self.tgt[0], self.tgt[2], params=W, backup_running_statistics=False, num_step=s, **self.tgt_kw))
         parts = crit(pred, self.tgt[1])
         own = [self.theta[k] for k in self.unrouted]
         g = torch.autograd.grad(parts['total'].sum(), [W[k] for k in self.routed] + own, allow_unused=True)
@@ -242,6 +252,13 @@ class GraphedInnerLoop:
             dst[T:2 * T].copy_(pick(ib))
         for dst, i in zip(self.tgt, tix):
             dst.copy_(pick(i))
+        if self.sup_kw:
+            # the fronts of THIS call's frames, in place at the addresses the graphs read (not captured: the frozen nets' routes and
+            # allocations are the eager ones); then the running-statistics updates of the passes the replays stand for
+            self.net.front(self.sup[0], self.sup[2], out=self.sup_kw['front'])
+            self.net.front(self.tgt[0], self.tgt[2], out=self.tgt_kw['front'])
+            self.net.replay_running_stats(self.sup_kw['front'], self.tgt_kw['front'], T,
+                                          sysm._front_passes(self.S, self.msl and self.training, self.training))
         with torch.no_grad():
             if T == 1:
                 if self._theta_to_w0 is None:

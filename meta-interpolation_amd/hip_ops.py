@@ -923,6 +923,25 @@ def filter_interpolation(input, flow, filt):
     return _FilterInterpolation.apply(input.contiguous(), flow.contiguous(), filt.contiguous())
 
 
+def filter_interpolation_into(out, c_off, input, flow, filt):
+    """filter_interpolation(input, flow, filt) written into channels [c_off, c_off + C) of ``out`` [B,C_total,H,W] (contiguous): the
+    same bits, no other channel touched, one launch and no temporary.  Forward only, as the frozen front of MetaDAIN needs it."""
+    input, flow, filt = input.contiguous(), flow.contiguous(), filt.contiguous()
+    _hip.require_cuda(out, input, flow, filt)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (out, input, flow, filt)):
+        raise NotImplementedError("filter_interpolation_into has no backward: it fills the rectify input of DAIN's frozen front "
+                                  "(meta_learning_system.py:96-101); call it under torch.no_grad()")
+    B, C, H, W = input.shape
+    if flow.shape != (B, 2, H, W) or filt.shape != (B, 16, H, W) or out.dim() != 4 or (out.shape[0], out.shape[2], out.shape[3]) != (B, H, W):
+        raise ValueError("filter_interpolation_into needs input [B,C,H,W], flow [B,2,H,W], a 4 x 4 filter [B,16,H,W] and out "
+                         "[B,C_total,H,W], got %s, %s, %s, %s" % (tuple(input.shape), tuple(flow.shape), tuple(filt.shape), tuple(out.shape)))
+    lib = _hip.lib()
+    _hip.launch("filterinterp_fwd_slice", lambda: _hip.check(lib.savfi_filterinterp_fwd_slice_f32(
+        input.data_ptr(), flow.data_ptr(), filt.data_ptr(), out.data_ptr(), B, C, H, W, 4, out.shape[1], int(c_off),
+        _hip.current_stream()), "savfi_filterinterp_fwd_slice_f32"), nbytes=filterinterp_bytes(B, C, H, W))
+    return out
+
+
 class _DepthFlowProjection(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input1, input2, fillhole):

@@ -1,7 +1,10 @@
 """python -m meta_interpolation_amd.main --model sepconv --synthetic ...   (reference: main.py:1-11)
 
 Under torch.distributed.run (one process per GPU) the meta-batch is sharded across ranks with one
-RCCL all-reduce of outer gradients per iteration; with a single process it is the sequential loop."""
+RCCL all-reduce of outer gradients per iteration; with a single process it is the sequential loop.
+
+--model dain adapts its tasks one by one in the eager loop unless --dain_task_modes 1 is given: then --task_batch, --graph_inner_loop and
+--task_streams mean for it what they mean for the other plugins (config.py; not with --second_order, not on the host)."""
 from .config import get_args
 from .data import MetaLearningSystemDataLoader
 from .experiment_builder import ExperimentBuilder

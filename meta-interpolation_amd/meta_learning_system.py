@@ -179,6 +179,10 @@ class SceneAdaptiveInterpolation(nn.Module):
                 raise NotImplementedError('Model not implemented yet!')
             print('Building %s model...' % args.model)
             self.net = MODEL_REGISTRY[args.model](args, not args.resume).to(self.device)
+        if int(getattr(args, 'dain_task_modes', 0) or 0) and hasattr(self.net, 'alloc_front'):
+            # --dain_task_modes 1: THIS MetaDAIN instance takes the lockstep and hipGraph paths (its class declines both)
+            self.net.lockstep_tasks = True
+            self.net.graph_capture = True
         if args.model == 'voxelflow':
             half = torch.full((3, 1, 1), 0.5 * 255, device=self.device)
             self.mean, self.std = half.clone(), half.clone()
@@ -479,11 +483,32 @@ class SceneAdaptiveInterpolation(nn.Module):
             theta = self.get_inner_loop_parameter_dict(self.net.named_parameters())
             fast = {k: v.detach().clone().requires_grad_() for k, v in theta.items()}
             x = torch.zeros((1,) + tuple(frame_shape), device=self.device)
-            out = self.net.forward(x, x, params=fast, backup_running_statistics=False, num_step=0)
+            out = self.net.forward(x, x, params=fast, backup_running_statistics=False, num_step=0, **self._probe_kw(frame_shape))
             out = out[0] if isinstance(out, tuple) else out
             g = torch.autograd.grad(out.sum(), list(fast.values()), allow_unused=True)
             self._routes = ([k for k, gi in zip(fast, g) if gi is not None], [k for k, gi in zip(fast, g) if gi is None])
         return self._routes
+
+    def _probe_kw(self, frame_shape):
+        """A plugin with a frozen front (dain) is probed on a zeroed throw-away front of its own: the probe then neither counts as a
+        front evaluation nor moves the depth net's running statistics."""
+        if not hasattr(self.net, 'alloc_front'):
+            return {}
+        return {'front': self.net.alloc_front(1, frame_shape[1], frame_shape[2], self.device), 'update_stats': False}
+
+    def _shared_fronts(self):
+        """Does the plugin have a frozen front that the lockstep / graph paths evaluate once per group and triplet?"""
+        return hasattr(self.net, 'front') and bool(getattr(self.net, 'reuse_front', False))
+
+    def _front_passes(self, num_steps, msl, training_phase):
+        """One task's forwards in the sequential loop's order, 's' = a support pass (pairs a, b), 't' = a target pass: what
+        MetaDAIN.replay_running_stats applies task by task after a group ran its passes with update_stats=False."""
+        passes = ['s'] if self.args.attenuate else []          # L2F: the embedding pass
+        for _ in range(num_steps):
+            passes += ['s', 't'] if msl else ['s']
+        if not training_phase or not msl:
+            passes.append('t')
+        return passes
 
     def _routing_known_incomplete(self):
         """True when the routing probe has run and found inner-loop tensors the plugin never reads from the fast dict (graphed
@@ -501,6 +526,8 @@ class SceneAdaptiveInterpolation(nn.Module):
             # one [n*T, ...] batch and hands 5-D stacked weights to MetaConv2dLayer, which is only right for a plugin whose
             # samples never interact (no train-mode BatchNorm) and that reads fast weights through the meta layers only
             return 0
+        if hasattr(self.net, 'front') and not self._shared_fronts():
+            return 0        # dain with reuse_front = False: the reference's structure, a front per pass, is the sequential loop's
         if not hasattr(self.criterion, 'per_sample'):
             return 0        # a user criterion without per-sample rows: the sequential loop calls it once per task
         if self.args.attenuate and self._routing(frame_shape)[1]:
@@ -530,12 +557,19 @@ class SceneAdaptiveInterpolation(nn.Module):
         tgt = [pick(i) for i in self.target_idxs]
 
         overlap = self.device.type == 'cuda' and bool(getattr(self.args, 'wgrad_overlap', 0))
+        # dain: ONE front for the group's [2T] support pairs and one for its [T] target pairs, handed to every pass; the passes leave
+        # the depth net's running statistics alone and the updates are replayed below in the sequential loop's order
+        sup_kw, tgt_kw = {}, {}
+        if self._shared_fronts():
+            sup_kw = {'front': self.net.front(sup[0], sup[2]), 'update_stats': False}
+            tgt_kw = {'front': self.net.front(tgt[0], tgt[2]), 'update_stats': False}
 
         def support_loss(weights, num_step):
             model_utils.set_own_params_const(True)      # first-order support pass: the plugin's own parameters are constants
             hip_ops.set_weight_gradient_overlap(overlap)    # weight gradients beside the data-gradient chain; joined below
             try:
-                out = self.net.forward(sup[0], sup[2], params=weights, backup_running_statistics=(num_step == 0), num_step=num_step)
+                out = self.net.forward(sup[0], sup[2], params=weights, backup_running_statistics=(num_step == 0), num_step=num_step,
+                                       **sup_kw)
             finally:
                 model_utils.set_own_params_const(False)
                 hip_ops.set_weight_gradient_overlap(False)
@@ -543,7 +577,7 @@ class SceneAdaptiveInterpolation(nn.Module):
             return self.criterion.per_sample(out, sup[1])['total'].sum()
 
         def target_pass(weights, num_step):
-            out = self.net.forward(tgt[0], tgt[2], params=weights, backup_running_statistics=False, num_step=num_step)
+            out = self.net.forward(tgt[0], tgt[2], params=weights, backup_running_statistics=False, num_step=num_step, **tgt_kw)
             out = out[0] if isinstance(out, tuple) else out
             return self.criterion.per_sample(out, tgt[1]), out
 
@@ -581,6 +615,8 @@ class SceneAdaptiveInterpolation(nn.Module):
             for k, v in parts.items():
                 for t in range(T):
                     logs[t].append((k, v[t]))
+        if sup_kw:
+            self.net.replay_running_stats(sup_kw['front'], tgt_kw['front'], T, self._front_passes(num_steps, msl, training_phase))
         per_task = torch.stack(task_terms, 0).sum(0)                            # [T]
         preds = preds.detach()
         results = []

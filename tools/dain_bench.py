@@ -1,7 +1,11 @@
 """HIP-event timing of the kernels of csrc/dainnet.hip and the Charbonnier loss against their ATen compositions, and of a whole DAIN
-meta-iteration with the frozen front reused and with the reuse switched off.
+meta-iteration with the frozen front reused and with the reuse switched off, of the same iteration with --dain_task_modes 1 (tasks in
+lockstep, eagerly and from captured graphs), and of front() with and without out=.
 
-    python tools/dain_bench.py [output file] [--iteration-size H W]        (needs the GPU)
+    python tools/dain_bench.py [output file] [--iteration-size H W] [--steps kernels,iteration,modes,front]        (needs the GPU)
+
+The steps run in the order given, each after the one before it has finished: an exception in a step ends the tool with a non-zero status
+and nothing further touches the GPU.  Lines are appended to the output file as each step completes.
 
 Kernels: at the hourglass's and the rectify net's shapes for 256 x 448 and 768 x 1280 frames (one task: the depth net's batch is the two
 frames of a pair), isolated launches, median and minimum of REPS launches after WARM warm-up calls; the ATen composition of the same
@@ -10,6 +14,9 @@ operand once) over the median time.
 Iteration: batch 6, one inner step, Adamax + Meta-SGD (scripts/run_dain.sh), synthetic frames, seeded weights; `reuse off` recomputes the
 front on every pass -- the reference's structure and the baseline.  Both systems hold the same weights; the two are timed alternately,
 ITERS iterations each after one warm-up iteration, a device synchronise around each.
+Modes: the same configuration with --dain_task_modes 1 and --task_batch 8 (one lockstep group of 6), --graph_inner_loop 0 (eager
+lockstep) and 1 (graphed lockstep), alternating with `front reused` (modes off, the default path), timed the same way; the graphed system
+gets one more warm-up iteration (its capture).  Front: front() for 6 pairs with and without out=alloc_front(...), HIP events.
 There is no speed gate anywhere: the figures say what was measured, on these shapes, nothing more.
 """
 import json
@@ -92,28 +99,59 @@ def kernels(lines):
             report("charbonnier_loss", (1, 3, H, W), 8 * p.numel(), *timed_pair(lambda: hip_ops.charbonnier_loss(p, q), aten_loss))
 
 
-def iteration(lines, H, W, batch=6):
+def _system(batch, reuse=True, **over):
     from meta_interpolation_amd.dain.networks.DAIN import MetaDAIN
     from meta_interpolation_amd.meta_learning_system import SceneAdaptiveInterpolation
     args = default_args(model='dain', num_gpu=1, loss='1*L1', optimizer='Adamax', metasgd=True, batch_size=batch, inner_lr=1e-5, outer_lr=1e-5,
-                        number_of_training_steps_per_iter=1, number_of_evaluation_steps_per_iter=1)
-    systems = {}
-    for name, reuse in (("front reused", True), ("reuse off (the reference's structure)", False)):
-        torch.manual_seed(1)
-        net = MetaDAIN()
-        synthetic.load_seeded_weights(net, 'dain')
-        net.reuse_front = reuse
-        systems[name] = SceneAdaptiveInterpolation(args, net=net)
+                        number_of_training_steps_per_iter=1, number_of_evaluation_steps_per_iter=1, **over)
+    torch.manual_seed(1)
+    net = MetaDAIN()
+    synthetic.load_seeded_weights(net, 'dain')
+    net.reuse_front = reuse
+    return SceneAdaptiveInterpolation(args, net=net)
+
+
+def iteration(lines, H, W, batch=6):
+    _iterations(lines, H, W, batch, {"front reused": _system(batch), "reuse off (the reference's structure)": _system(batch, reuse=False)})
+
+
+def modes(lines, H, W, batch=6):
+    """--dain_task_modes 1 beside the default path (`front reused` of iteration(): the parent commit's)."""
+    _iterations(lines, H, W, batch, {"front reused": _system(batch),
+                                     "task modes on, eager lockstep": _system(batch, dain_task_modes=1, graph_inner_loop=0, task_streams=1),
+                                     "task modes on, graphed lockstep": _system(batch, dain_task_modes=1, graph_inner_loop=1, task_streams=1)},
+                warm=2)
+
+
+def front(lines, H, W, batch=6):
+    from meta_interpolation_amd.dain.networks.DAIN import MetaDAIN
+    system = _system(1)
+    net = system.net
+    frames = [f.cuda() for f in synthetic.septuplet_batch(batch, H, W, model='dain')]
+    out = MetaDAIN.alloc_front(batch, H, W, 'cuda')
+    global REPS, WARM
+    keep, REPS, WARM = (REPS, WARM), 5, 1
+    try:
+        plain, inplace = timed_pair(lambda: net.front(frames[2], frames[4]), lambda: net.front(frames[2], frames[4], out=out))
+    finally:
+        REPS, WARM = keep
+    lines.append(json.dumps(dict(front="%d pairs at %dx%d" % (batch, H, W), median_ms=round(plain[0] / 1e3, 2), min_ms=round(plain[1] / 1e3, 2),
+                                 out_median_ms=round(inplace[0] / 1e3, 2), out_min_ms=round(inplace[1] / 1e3, 2),
+                                 plain_over_out=round(plain[0] / inplace[0], 3), repetitions=5)))
+    print(lines[-1], flush=True)
+
+
+def _iterations(lines, H, W, batch, systems, warm=1):
     frames = [f.cuda() for f in synthetic.septuplet_batch(batch, H, W, model='dain')]
     times = {name: [] for name in systems}
-    for it in range(ITERS + 1):
+    for it in range(ITERS + warm):
         for name, system in systems.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             losses, _, _ = system.run_train_iter(frames, 0)
             float(losses['loss'])
             torch.cuda.synchronize()
-            if it:
+            if it >= warm:
                 times[name].append(time.perf_counter() - t0)
     med = {}
     for name, t in times.items():
@@ -121,11 +159,12 @@ def iteration(lines, H, W, batch=6):
         med[name] = t[len(t) // 2]
         lines.append(json.dumps(dict(iteration=name, frames="%dx%d" % (H, W), batch=batch, inner_steps=1, median_ms=round(1e3 * med[name], 1),
                                      min_ms=round(1e3 * t[0], 1), iterations=len(t),
-                                     fronts_per_iteration=systems[name].net.front_evaluations // (ITERS + 1))))
+                                     fronts_per_iteration=systems[name].net.front_evaluations // (ITERS + warm))))
         print(lines[-1], flush=True)
     names = list(systems)
-    lines.append("# %dx%d: reuse off / front reused = %.2f (medians)" % (H, W, med[names[1]] / med[names[0]]))
-    print(lines[-1], flush=True)
+    for other in names[1:]:
+        lines.append("# %dx%d: %s / %s = %.2f (medians)" % (H, W, other, names[0], med[other] / med[names[0]]))
+        print(lines[-1], flush=True)
 
 
 def main():
@@ -137,17 +176,30 @@ def main():
         i = argv.index('--iteration-size')
         size = (int(argv[i + 1]), int(argv[i + 2]))
         del argv[i:i + 3]
+    steps = ['kernels', 'iteration', 'modes', 'front']
+    if '--steps' in argv:
+        i = argv.index('--steps')
+        steps = argv[i + 1].split(',')
+        del argv[i:i + 2]
     out_path = argv[0] if argv else None
-    lines = []
-    kernels(lines)
-    iteration(lines, *size)
-    if out_path:
+    table = {'kernels': lambda ls: kernels(ls), 'iteration': lambda ls: iteration(ls, *size), 'modes': lambda ls: modes(ls, *size),
+             'front': lambda ls: front(ls, *size)}
+    unknown = [st for st in steps if st not in table]
+    if unknown:
+        raise SystemExit("unknown step(s) %s: one of %s" % (unknown, sorted(table)))
+    if out_path and not os.path.exists(out_path):
         with open(out_path, "w") as fh:
             fh.write("# tools/dain_bench.py on an MI355X.  Kernels: isolated launches, HIP events, %d repetitions after %d warm-up calls, alternating\n"
                      "# with the ATen composition; fraction of the 8 TB/s HBM peak = algorithmic bytes / median time / 8e12.  Iteration: host clock\n"
-                     "# around run_train_iter with a device synchronise, %d iterations after one warm-up, the two variants alternating.\n"
+                     "# around run_train_iter with a device synchronise, %d iterations after the warm-up, the variants alternating.\n"
                      "# Measured on these shapes only; no speed gate.\n" % (REPS, WARM, ITERS))
-            fh.write("\n".join(lines) + "\n")
+    for st in steps:             # one after the other: an exception ends the tool, nothing later runs on the GPU
+        lines = []
+        table[st](lines)
+        torch.cuda.synchronize()
+        if out_path:
+            with open(out_path, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
