@@ -29,15 +29,15 @@ import contextlib
 
 import torch
 
-from . import _hip, hip_ops, model_utils, utils
+from . import _hip, hip_ops
+from .task_schedule import autograd_mode, target_schedule, task_picker
 
 
-# Graphed L2F is OPT-IN (SAVFI_GRAPH_L2F=1).  It matches the eager loop and the reference fixtures from 64x64 to 1280x720
+# Graphed L2F is OPT-IN (the module attribute GRAPH_L2F below).  It matches the eager loop and the reference fixtures from 64x64 to 1280x720
 # (tests/test_system_gpu.py, tests/test_fullsize_gpu.py::test_graphed_cain_720p_follows_changing_frames,
 # profiles/r03_graphed_l2f_720p.txt) -- the garbage its third replay returned at 720p earlier this round was a stale captured
 # mean (ATen's x.mean(2) behind a hipGraph memset node, which only clears once on ROCm 7.2: csrc/submean.hip) -- but config C5 is
 # GPU-bound and gains nothing from it (6.93 vs 6.91 steps/s), so the default keeps the eager loop, where kernels can be timed in place.
-import os as _os
 GRAPH_L2F = False      # tools/graph_vs_eager.py, tools/memset_capture_audit.py set it: L2F from graph replays (DESIGN: the ROCm 7.2 memset-node finding)
 
 
@@ -53,23 +53,17 @@ def supported(system, use_second_order):
             and hasattr(system.inner_loop_optimizer, 'lr_mode'))
 
 
-def _frame(out):
-    """Super SloMo's forward returns (frame, extras for its 'Super' loss): the frame is what this path uses."""
-    return out[0] if isinstance(out, tuple) else out
-
-
 class GraphedInnerLoop:
     def __init__(self, system, frame_shape, num_steps, training, msl, tasks=1):
         self.sys = system
         self.T = int(tasks)
         self.net, self.rule, self.crit = system.net, system.inner_loop_optimizer, system.criterion
         self.S, self.training, self.msl = num_steps, training, msl
+        self.schedule = target_schedule(num_steps, msl, training)      # the set's target graphs
         self.shape = tuple(frame_shape)            # (3, H, W)
         dev = system.device
-        named = system.get_inner_loop_parameter_dict(self.net.named_parameters())
-        self.all_keys = list(named.keys())
-        self.theta = named
-        self._probe_routing()
+        self.theta = system.get_inner_loop_parameter_dict(self.net.named_parameters())
+        self.routed, self.unrouted = system._routing(self.shape)
         C, H, W = self.shape
         T = self.T
         self.sup = [torch.zeros(2 * T, C, H, W, device=dev) for _ in range(3)]      # frame0 | target | frame1, pair batch
@@ -102,18 +96,6 @@ class GraphedInnerLoop:
         self._capture()
 
     # ------------------------------------------------------------------------------------------
-    def _probe_routing(self):
-        """Which inner-loop tensors does the plugin actually read from the fast dict?  (SepConv 54 of 94,
-        VoxelFlow 9 of 23, CAIN 494 of 494: SURVEY.md fact 6.)  One eager forward on cloned tensors."""
-        C, H, W = self.shape
-        dev = self.sys.device
-        fast = {k: v.detach().clone().requires_grad_() for k, v in self.theta.items()}
-        x = torch.zeros(1, C, H, W, device=dev)
-        out = _frame(self.net.forward(x, x, params=fast, backup_running_statistics=False, num_step=0, **self.sys._probe_kw(self.shape)))
-        g = torch.autograd.grad(out.sum(), list(fast.values()), allow_unused=True)
-        self.routed = [k for k, gi in zip(self.all_keys, g) if gi is not None]
-        self.unrouted = [k for k, gi in zip(self.all_keys, g) if gi is None]
-
     def _lrs(self, t):
         return [self.rule._lr(k, t) for k in self.routed]
 
@@ -123,12 +105,8 @@ class GraphedInnerLoop:
             # mt_update (the plan is keyed by the list's shapes, which W_0 shares with every W_t); 127 single-layer launches per
             # replay of CAIN's step graph otherwise
             hip_ops.filters_after_update([W[k] for k in self.routed])
-        model_utils.set_own_params_const(True)      # first-order support pass: non-routed parameters are constants
-        try:
-            out = _frame(self.net.forward(self.sup[0], self.sup[2], params=W, backup_running_statistics=(t == 0), num_step=t,
-                                          **self.sup_kw))
-        finally:
-            model_utils.set_own_params_const(False)
+        # first-order support pass: non-routed parameters are constants; no weight gradients on a side stream inside a capture
+        out = self.sys._run_pass(self.sup[0], self.sup[2], W, t, support=True, own_const=True, front_kw=self.sup_kw)
         if self.T == 1:
             loss = self.crit(out[0:1], self.sup[1][0:1])['total'] + self.crit(out[1:2], self.sup[1][1:2])['total']
         else:
@@ -147,106 +125,74 @@ class GraphedInnerLoop:
     def _embedding(self, W):
         """L2F task embedding (reference meta_learning_system.py:231-255): support loss at theta, first-order gradients, one
         fused per-tensor mean."""
-        model_utils.set_own_params_const(True)
-        try:
-            out = _frame(self.net.forward(self.sup[0], self.sup[2], params=W, backup_running_statistics=True, num_step=0, **self.sup_kw))
-        finally:
-            model_utils.set_own_params_const(False)
+        out = self.sys._run_pass(self.sup[0], self.sup[2], W, 0, support=True, own_const=True, front_kw=self.sup_kw)
         loss = self.crit(out[0:1], self.sup[1][0:1])['total'] + self.crit(out[1:2], self.sup[1][1:2])['total']
         g = torch.autograd.grad(loss, [W[k] for k in self.routed])
         return hip_ops.mt_mean(g)
 
     def _target(self, W, s, with_grad):
         crit = self.crit if self.T == 1 else self.crit.per_sample          # T > 1: every loss part is a [T] vector
-        if not with_grad:
-            with torch.no_grad():
-                pred = _frame(self.net.forward(self.tgt[0], self.tgt[2], params=W, backup_running_statistics=False, num_step=s,
-                                               **self.tgt_kw))
-                parts = crit(pred, self.tgt[1])
-            return dict(pred=pred, parts={k: v.detach() for k, v in parts.items()})
-        pred = _frame(self.net.forward(self.tgt[0], self.tgt[2], params=W, backup_running_statistics=False, num_step=s, **self.tgt_kw))
-        parts = crit(pred, self.tgt[1])
-        own = [self.theta[k] for k in self.unrouted]
-        g = torch.autograd.grad(parts['total'].sum(), [W[k] for k in self.routed] + own, allow_unused=True)
-        n = len(self.routed)
-        return dict(pred=pred.detach(), parts={k: v.detach() for k, v in parts.items()}, g_routed=list(g[:n]),
-                    g_own=list(g[n:]))
+        with autograd_mode(with_grad):
+            pred = self.sys._run_pass(self.tgt[0], self.tgt[2], W, s, support=False, front_kw=self.tgt_kw)
+            parts = crit(pred, self.tgt[1])
+        out = dict(pred=pred.detach(), parts={k: v.detach() for k, v in parts.items()})
+        if with_grad:
+            own = [self.theta[k] for k in self.unrouted]
+            g = torch.autograd.grad(parts['total'].sum(), [W[k] for k in self.routed] + own, allow_unused=True)
+            n = len(self.routed)
+            out.update(g_routed=list(g[:n]), g_own=list(g[n:]))
+        return out
 
     def _capture(self):
-        need_target = sorted(set(range(1, self.S + 1)) if (self.msl and self.training) else {self.S})
-        with_grad = self.training
+        due = {s: with_grad for s, _, with_grad in self.schedule}
 
-        def run_all():
+        def run_all(scope):
+            """Every pass of the set in order, each inside its own `scope()` -> (embedding, steps, targets) as (graph, outputs)."""
             W = self.W0
-            outs, tg = [], {}
+            emb, steps, targets = (None, None), [], {}
             if self.attenuate:
-                self._embedding(W)
-            for t in range(self.S):
-                o = self._support_step(W, t)
-                outs.append(o)
-                W = o['W']
-                if (t + 1) in need_target:
-                    tg[t + 1] = self._target(W, t + 1, with_grad)
-            if 0 in need_target or self.S == 0:
-                tg[self.S] = self._target(W, self.S, with_grad)
-            return outs, tg
+                with scope() as g:
+                    emb = (g, self._embedding(W))
+            for s in range(self.S + 1):
+                if s:
+                    with scope() as g:
+                        o = self._support_step(W, s - 1)
+                    steps.append((g, o))
+                    W = o['W']
+                if s in due:
+                    with scope() as g:
+                        targets[s] = (g, self._target(W, s, due[s]))
+            return emb, steps, targets
 
         # warm-up on a side stream (MIOpen find, lazy inits), never on the default stream
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
-                run_all()
+                run_all(contextlib.nullcontext)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
 
         self.pool = torch.cuda.graph_pool_handle()
-        W = self.W0
-        if self.attenuate:
-            with self._captured('embedding') as g:
-                self.emb_out = self._embedding(W)
-            self.emb_graph = g
-        for t in range(self.S):
-            with self._captured('step%d' % t) as g:
-                o = self._support_step(W, t)
-            self.step_graphs.append(g)
-            self.step_out.append(o)
-            W = o['W']
-            if (t + 1) in need_target:
-                with self._captured('target%d' % (t + 1)) as tgph:
-                    to = self._target(W, t + 1, with_grad)
-                self.target_graphs[t + 1] = (tgph, to)
-        if self.S == 0:
-            with self._captured('target0') as tgph:
-                to = self._target(W, 0, with_grad)
-            self.target_graphs[0] = (tgph, to)
+        (self.emb_graph, self.emb_out), steps, self.target_graphs = run_all(self._captured)
+        self.step_graphs, self.step_out = [g for g, _ in steps], [o for _, o in steps]
 
     @contextlib.contextmanager
-    def _captured(self, tag):
+    def _captured(self):
         """One capture into the shared pool."""
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self.pool):
             yield g
 
     # ------------------------------------------------------------------------------------------
-    def run_task(self, frames, task_id, importance, accum):
-        """Adapt on one task (T = 1) and (when training) add its outer-gradient contribution to `accum`.
-        Returns (task_loss scalar tensor, pred [1,3,H,W], list of loss-part dicts)."""
-        losses, preds, logs = self.run_tasks(frames, [task_id], importance, accum)
-        return losses[0], preds[0:1], logs[0]
-
     def run_tasks(self, frames, ids, importance, accum):
-        """Adapt the T tasks `ids` together; returns (task losses [T], preds [T,3,H,W], per task a list of loss-part dicts)."""
+        """Adapt the T tasks `ids` together; returns (task losses [T], preds [T,3,H,W], per task a list of (loss part, value))."""
         sysm = self.sys
         T = self.T
         assert len(ids) == T, (ids, T)
         a, b = sysm.support_idxs
         tix = sysm.target_idxs
-        if list(ids) == list(range(ids[0], ids[0] + T)):
-            pick = lambda i: frames[i][ids[0]:ids[0] + T]
-        else:
-            sel = torch.as_tensor(list(ids), device=frames[0].device)
-            pick = lambda i: frames[i].index_select(0, sel)
+        pick = task_picker(frames, ids)
         for dst, (ia, ib) in zip(self.sup, ((a[0], b[0]), (a[1], b[1]), (a[2], b[2]))):
             dst[0:T].copy_(pick(ia))           # sample-major: sample j * T + t belongs to task t
             dst[T:2 * T].copy_(pick(ib))
@@ -258,7 +204,7 @@ class GraphedInnerLoop:
             self.net.front(self.sup[0], self.sup[2], out=self.sup_kw['front'])
             self.net.front(self.tgt[0], self.tgt[2], out=self.tgt_kw['front'])
             self.net.replay_running_stats(self.sup_kw['front'], self.tgt_kw['front'], T,
-                                          sysm._front_passes(self.S, self.msl and self.training, self.training))
+                                          sysm._front_passes(self.S, self.msl, self.training))
         with torch.no_grad():
             if T == 1:
                 if self._theta_to_w0 is None:
@@ -281,16 +227,14 @@ class GraphedInnerLoop:
             with torch.no_grad():
                 hip_ops.mt_scale_into(gamma, [self.theta[k] for k in self.routed], [self.W0[k] for k in self.routed])
         # replay: S support steps, target passes where needed
-        for t in range(self.S):
-            self.step_graphs[t].replay()
-            if (t + 1) in self.target_graphs:
-                self.target_graphs[t + 1][0].replay()
-        if self.S == 0:
-            self.target_graphs[0][0].replay()
+        for s in range(self.S + 1):
+            if s:
+                self.step_graphs[s - 1].replay()
+            if s in self.target_graphs:
+                self.target_graphs[s][0].replay()
 
         # losses / outer gradients from the static outputs
-        msl = self.msl and self.training
-        weights = {s: (importance[s - 1] if msl else 1.0) for s in self.target_graphs}
+        weights = {s: (1.0 if index is None else importance[index]) for s, index, _ in self.schedule}
         for s, (_, to) in sorted(self.target_graphs.items()):
             w = weights[s]
             term = w * to['parts']['total']
@@ -335,9 +279,8 @@ class GraphedInnerLoop:
                 # identity chain W_S -> ... -> W_0 = theta broadcast over the tasks: the task axis is summed
                 accum.add_params(self.routed, suffix if T == 1 else [x.sum(0) for x in suffix], owned=True)
         if T == 1:
-            return task_loss.reshape(1), pred.clone(), [logs]
-        per_task_logs = [[{k: v[t] for k, v in parts.items()} for parts in logs] for t in range(T)]
-        return task_loss, pred.clone(), per_task_logs
+            return task_loss.reshape(1), pred.clone(), [[kv for parts in logs for kv in parts.items()]]
+        return task_loss, pred.clone(), [[(k, v[t]) for parts in logs for k, v in parts.items()] for t in range(T)]
 
 
 class OuterGradAccumulator:

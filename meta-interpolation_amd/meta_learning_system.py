@@ -19,7 +19,9 @@ What is different (MI355X-first, results identical):
     with a single process this is the reference's sequential loop.  The reference's ``.module`` call
     for >1 visible device (:285-287) is not reproduced: one process owns one device.
 """
+import contextlib
 import functools
+import gc
 import os
 import threading
 
@@ -32,6 +34,7 @@ from . import _hip, graph_inner_loop, hip_ops, model_utils, utils
 from .inner_loop_optimizers import LSLRGradientDescentLearningRule, MetaSGDLearningRule
 from .loss import CharbonnierLoss, Loss
 from .task_parallel import TaskParallel
+from .task_schedule import autograd_mode, target_schedule, task_picker
 
 
 def set_torch_seed(seed):
@@ -319,12 +322,38 @@ class SceneAdaptiveInterpolation(nn.Module):
             fronts[key] = self.net.front(frame0, frame1)
         return {'front': fronts[key]}
 
-    def net_forward(self, frame0, frame1, target, weights, backup_running_statistics, training, num_step, front_kw=None):
+    @contextlib.contextmanager
+    def _pass_flags(self, own_const, overlap):
+        """The op layer's two per-pass switches (thread-local there) for the duration of a pass.  own_const: the plugin's own
+        parameters, the tensors it does not read from the fast dict, are constants.  overlap: the weight gradients of the pass
+        may run beside its data-gradient chain; whoever calls autograd.grad joins them before anything reads them."""
+        model_utils.set_own_params_const(own_const)
+        hip_ops.set_weight_gradient_overlap(overlap)
+        try:
+            yield
+        finally:
+            model_utils.set_own_params_const(False)
+            hip_ops.set_weight_gradient_overlap(False)
+
+    def _run_pass(self, frame0, frame1, weights, num_step, *, support, own_const=False, overlap=False, front_kw=None,
+                  extras=False, flags=True):
+        """THE plugin forward of every task mode: a support pass (which backs up the running statistics at step 0) or a target
+        pass on the fast weights -> the frame, with extras=True (frame, Super SloMo's flows and warped frames for its 'Super'
+        loss, or None).  flags=False: the caller holds _pass_flags itself, over more than one pass."""
+        with self._pass_flags(own_const, overlap) if flags else contextlib.nullcontext():
+            out = self.net.forward(frame0, frame1, params=weights, backup_running_statistics=support and num_step == 0,
+                                   num_step=num_step, **(front_kw or {}))
+        frame, extra = out if isinstance(out, tuple) else (out, None)
+        return (frame, extra) if extras else frame
+
+    def _wgrad_overlap(self):
+        return self.device.type == 'cuda' and bool(getattr(self.args, 'wgrad_overlap', 0))
+
+    def net_forward(self, frame0, frame1, target, weights, num_step, *, support, front_kw=None, flags=True):
         """One backbone pass with fast weights + criterion -> (losses dict, output)  (reference :475-509)."""
-        output = self.net.forward(frame0, frame1, params=weights,
-                                  backup_running_statistics=backup_running_statistics, num_step=num_step, **(front_kw or {}))
-        if isinstance(output, tuple):     # superslomo: (frame, flows and warped frames for the 'Super' loss)  (:499-502)
-            output, extras = output
+        output, extras = self._run_pass(frame0, frame1, weights, num_step, support=support, front_kw=front_kw, extras=True,
+                                        flags=flags)
+        if extras is not None:            # superslomo: flows and warped frames for the 'Super' loss  (:499-502)
             return self.criterion(output, target, I0=frame0, I1=frame1, **extras), output
         return self.criterion(output, target), output
 
@@ -333,46 +362,31 @@ class SceneAdaptiveInterpolation(nn.Module):
         a, b = self.support_idxs
         # step 0 differentiates w.r.t. theta itself, whose non-routed tensors ARE the modules' own parameters
         # (reference fact: 94 live tensors at step 0, 54 afterwards); from step 1 on those are constants
-        model_utils.set_own_params_const(self._first_order and num_step > 0)
-        # first-order support pass: its weight gradients may run beside the data-gradient chain (joined by the callers
-        # right after autograd.grad, before anything reads them)
-        hip_ops.set_weight_gradient_overlap(self._first_order and self.device.type == 'cuda'
-                                            and bool(getattr(self.args, 'wgrad_overlap', 0)))
-        try:
-            return self._support_loss_impl(frames, task_id, weights, num_step, a, b, fronts)
-        finally:
-            model_utils.set_own_params_const(False)
-            hip_ops.set_weight_gradient_overlap(False)
-
-    def _support_loss_impl(self, frames, task_id, weights, num_step, a, b, fronts=None):
+        own_const = self._first_order and num_step > 0
+        overlap = self._first_order and self._wgrad_overlap()
         if self.fuse_support_pairs:
             sl = slice(task_id, task_id + 1)
             f0 = torch.cat([frames[a[0]][sl], frames[b[0]][sl]], 0)
             f1 = torch.cat([frames[a[2]][sl], frames[b[2]][sl]], 0)
-            out = self.net.forward(f0, f1, params=weights, backup_running_statistics=(num_step == 0),
-                                   num_step=num_step, **self._front_kw(fronts, 'support', f0, f1))
-            if isinstance(out, tuple):    # superslomo; its extras only feed the 'Super' loss, which Loss rejects
-                out = out[0]
-            la = self.criterion(out[0:1], frames[a[1]][sl])
-            lb = self.criterion(out[1:2], frames[b[1]][sl])
-            return la['total'] + lb['total']
+            # superslomo's extras only feed the 'Super' loss, which Loss rejects
+            out = self._run_pass(f0, f1, weights, num_step, support=True, own_const=own_const, overlap=overlap,
+                                 front_kw=self._front_kw(fronts, 'support', f0, f1))
+            return self.criterion(out[0:1], frames[a[1]][sl])['total'] + self.criterion(out[1:2], frames[b[1]][sl])['total']
         total = 0
-        for which, ind in enumerate((a, b)):
-            f0, f1 = frames[ind[0]][task_id].unsqueeze(0), frames[ind[2]][task_id].unsqueeze(0)
-            losses, _ = self.net_forward(frame0=f0, frame1=f1,
-                                         target=frames[ind[1]][task_id].unsqueeze(0), weights=weights,
-                                         backup_running_statistics=(num_step == 0), training=True,
-                                         num_step=num_step, front_kw=self._front_kw(fronts, 'support%d' % which, f0, f1))
-            total = total + losses['total']
+        with self._pass_flags(own_const, overlap):      # ONE scope: a weight both passes read is counted over both (hip_ops._WG.uses)
+            for which, ind in enumerate((a, b)):
+                f0, f1 = frames[ind[0]][task_id].unsqueeze(0), frames[ind[2]][task_id].unsqueeze(0)
+                losses, _ = self.net_forward(f0, f1, frames[ind[1]][task_id].unsqueeze(0), weights, num_step, support=True,
+                                             front_kw=self._front_kw(fronts, 'support%d' % which, f0, f1), flags=False)
+                total = total + losses['total']
         return total
 
-    def _target_pass(self, frames, task_id, weights, num_step, fronts=None):
+    def _target_pass(self, frames, task_id, weights, num_step, fronts=None, with_grad=True):
         t = self.target_idxs
         f0, f1 = frames[t[0]][task_id].unsqueeze(0), frames[t[2]][task_id].unsqueeze(0)
-        return self.net_forward(frame0=f0, frame1=f1,
-                                target=frames[t[1]][task_id].unsqueeze(0), weights=weights,
-                                backup_running_statistics=False, training=True, num_step=num_step,
-                                front_kw=self._front_kw(fronts, 'target', f0, f1))
+        with autograd_mode(with_grad):
+            return self.net_forward(f0, f1, frames[t[1]][task_id].unsqueeze(0), weights, num_step, support=False,
+                                    front_kw=self._front_kw(fronts, 'target', f0, f1))
 
     # -----------------------------------------------------------------------------------------
     # L2F
@@ -410,20 +424,23 @@ class SceneAdaptiveInterpolation(nn.Module):
             names_grads_wrt_params_dict=dict(zip(names_weights_copy.keys(), grads)),
             num_step=current_step_idx)
 
-    def _adapt(self, frames, task_id, num_steps, use_second_order, per_step_hook=None, fronts=None):
-        """Run the inner loop of one task; returns the adapted fast weights.  fronts: the task's {triplet: front} (_front_kw)."""
+    def _adapt(self, frames, task_id, num_steps, use_second_order, on_weights=None, fronts=None):
+        """Run the inner loop of one task; returns the adapted fast weights.  on_weights(s, W_s) sees the weights after s = 0 ..
+        num_steps updates.  fronts: the task's {triplet: front} (_front_kw)."""
         weights = self.get_inner_loop_parameter_dict(self.net.named_parameters())
         weights = {name.replace('module.', ''): v for name, v in weights.items()}
         self.inner_loop_optimizer.initialize_state()
         if self.args.attenuate:
             emb = self.get_task_embeddings(frames, task_id, weights, fronts)
             weights = self.attenuate_init(task_embeddings=emb, names_weights_copy=weights)
+        if on_weights is not None:
+            on_weights(0, weights)
         for num_step in range(num_steps):
             support_loss = self._support_loss(frames, task_id, weights, num_step, fronts)
             weights = self.apply_inner_loop_update(loss=support_loss, names_weights_copy=weights,
                                                    use_second_order=use_second_order, current_step_idx=num_step)
-            if per_step_hook is not None:
-                per_step_hook(num_step, weights)
+            if on_weights is not None:
+                on_weights(num_step + 1, weights)
         return weights
 
     def _to_unit_range(self, img):
@@ -444,24 +461,16 @@ class SceneAdaptiveInterpolation(nn.Module):
         task_losses, logs, state = [], [], {}
         fronts = {} if hasattr(self.net, 'front') else None       # this task's frozen fronts, one per triplet (dain)
 
-        def after_step(num_step, weights):
-            if msl:  # MAML++: weighted target loss after every inner step
-                tl, tp_ = self._target_pass(frames, task_id, weights, num_step, fronts)
-                task_losses.append(importance[num_step] * tl['total'])
+        due = {s: (index, with_grad) for s, index, with_grad in target_schedule(num_steps, msl, training_phase)}
+
+        def target(s, weights):
+            if s in due:
+                index, with_grad = due[s]        # a multi-step-loss pass on W_s is handed num_step = s - 1 (target_schedule)
+                tl, state['preds'] = self._target_pass(frames, task_id, weights, s if index is None else s - 1, fronts, with_grad)
+                task_losses.append(tl['total'] if index is None else importance[index] * tl['total'])
                 logs.extend(tl.items())
-                state['preds'] = tp_
 
-        weights = self._adapt(frames, task_id, num_steps, use_second_order, after_step, fronts)
-
-        if not training_phase:
-            with torch.no_grad():
-                tl, state['preds'] = self._target_pass(frames, task_id, weights, num_steps, fronts)
-            task_losses.append(tl['total'])
-            logs.extend(tl.items())
-        elif not msl:
-            tl, state['preds'] = self._target_pass(frames, task_id, weights, num_steps, fronts)
-            task_losses.append(tl['total'])
-            logs.extend(tl.items())
+        self._adapt(frames, task_id, num_steps, use_second_order, target, fronts)
 
         target_preds = state['preds']
         res = {'pred': self._to_unit_range(target_preds.detach().squeeze(0)).unsqueeze(0), 'logs': logs}
@@ -483,8 +492,7 @@ class SceneAdaptiveInterpolation(nn.Module):
             theta = self.get_inner_loop_parameter_dict(self.net.named_parameters())
             fast = {k: v.detach().clone().requires_grad_() for k, v in theta.items()}
             x = torch.zeros((1,) + tuple(frame_shape), device=self.device)
-            out = self.net.forward(x, x, params=fast, backup_running_statistics=False, num_step=0, **self._probe_kw(frame_shape))
-            out = out[0] if isinstance(out, tuple) else out
+            out = self._run_pass(x, x, fast, 0, support=False, front_kw=self._probe_kw(frame_shape))
             g = torch.autograd.grad(out.sum(), list(fast.values()), allow_unused=True)
             self._routes = ([k for k, gi in zip(fast, g) if gi is not None], [k for k, gi in zip(fast, g) if gi is None])
         return self._routes
@@ -503,11 +511,10 @@ class SceneAdaptiveInterpolation(nn.Module):
     def _front_passes(self, num_steps, msl, training_phase):
         """One task's forwards in the sequential loop's order, 's' = a support pass (pairs a, b), 't' = a target pass: what
         MetaDAIN.replay_running_stats applies task by task after a group ran its passes with update_stats=False."""
+        due = {s for s, _, _ in target_schedule(num_steps, msl, training_phase)}
         passes = ['s'] if self.args.attenuate else []          # L2F: the embedding pass
-        for _ in range(num_steps):
-            passes += ['s', 't'] if msl else ['s']
-        if not training_phase or not msl:
-            passes.append('t')
+        for s in range(num_steps + 1):
+            passes += ['s'] * (s > 0) + ['t'] * (s in due)      # the step that makes W_s, then the target pass on it
         return passes
 
     def _routing_known_incomplete(self):
@@ -547,16 +554,13 @@ class SceneAdaptiveInterpolation(nn.Module):
         T = len(ids)
         routed, _ = self._routing(frames[0].shape[1:])
         theta = self.get_inner_loop_parameter_dict(self.net.named_parameters())
-        sel = torch.as_tensor(ids, device=self.device)
-        consecutive = list(ids) == list(range(ids[0], ids[0] + T))
-        pick = (lambda i: frames[i][ids[0]:ids[0] + T]) if consecutive else (lambda i: frames[i].index_select(0, sel))
+        pick = task_picker(frames, ids)
         W = {k: theta[k].unsqueeze(0).expand(T, *theta[k].shape).contiguous() for k in routed}
         self.inner_loop_optimizer.initialize_state()
         a, b = self.support_idxs
         sup = [torch.cat([pick(a[i]), pick(b[i])], 0) for i in range(3)]           # frame0 | target | frame1, [2T,3,H,W]
         tgt = [pick(i) for i in self.target_idxs]
 
-        overlap = self.device.type == 'cuda' and bool(getattr(self.args, 'wgrad_overlap', 0))
         # dain: ONE front for the group's [2T] support pairs and one for its [T] target pairs, handed to every pass; the passes leave
         # the depth net's running statistics alone and the updates are replayed below in the sequential loop's order
         sup_kw, tgt_kw = {}, {}
@@ -565,21 +569,25 @@ class SceneAdaptiveInterpolation(nn.Module):
             tgt_kw = {'front': self.net.front(tgt[0], tgt[2]), 'update_stats': False}
 
         def support_loss(weights, num_step):
-            model_utils.set_own_params_const(True)      # first-order support pass: the plugin's own parameters are constants
-            hip_ops.set_weight_gradient_overlap(overlap)    # weight gradients beside the data-gradient chain; joined below
-            try:
-                out = self.net.forward(sup[0], sup[2], params=weights, backup_running_statistics=(num_step == 0), num_step=num_step,
-                                       **sup_kw)
-            finally:
-                model_utils.set_own_params_const(False)
-                hip_ops.set_weight_gradient_overlap(False)
-            out = out[0] if isinstance(out, tuple) else out
+            # first-order support pass: the plugin's own parameters are constants, weight gradients beside the data-gradient chain
+            out = self._run_pass(sup[0], sup[2], weights, num_step, support=True, own_const=True, overlap=self._wgrad_overlap(),
+                                 front_kw=sup_kw)
             return self.criterion.per_sample(out, sup[1])['total'].sum()
 
-        def target_pass(weights, num_step):
-            out = self.net.forward(tgt[0], tgt[2], params=weights, backup_running_statistics=False, num_step=num_step, **tgt_kw)
-            out = out[0] if isinstance(out, tuple) else out
-            return self.criterion.per_sample(out, tgt[1]), out
+        due = {s: (index, with_grad) for s, index, with_grad in target_schedule(num_steps, msl, training_phase)}
+        task_terms, logs, state = [], [[] for _ in range(T)], {}
+
+        def target(s, weights):
+            if s in due:
+                index, with_grad = due[s]        # a multi-step-loss pass on W_s is handed num_step = s - 1 (target_schedule)
+                with autograd_mode(with_grad):
+                    state['preds'] = self._run_pass(tgt[0], tgt[2], weights, s if index is None else s - 1, support=False,
+                                                    front_kw=tgt_kw)
+                    parts = self.criterion.per_sample(state['preds'], tgt[1])
+                task_terms.append(parts['total'] if index is None else importance[index] * parts['total'])
+                for k, v in parts.items():
+                    for t in range(T):
+                        logs[t].append((k, v[t]))
 
         if self.args.attenuate:        # L2F per task: embedding [T, L] -> gamma [T, L] -> w_i <- gamma_i * w_i
             keys = list(W)
@@ -591,7 +599,7 @@ class SceneAdaptiveInterpolation(nn.Module):
             gamma.clamp_(0, 1)
             W = {k: gamma[:, i].reshape((T,) + (1,) * (W[k].dim() - 1)) * W[k] for i, k in enumerate(keys)}
 
-        task_terms, logs, preds = [], [[] for _ in range(T)], None
+        target(0, W)
         for num_step in range(num_steps):
             loss = support_loss(W, num_step)
             keys = list(W)
@@ -599,37 +607,48 @@ class SceneAdaptiveInterpolation(nn.Module):
             hip_ops.join_weight_gradients()
             W = self.inner_loop_optimizer.update_params(names_weights_dict=W, names_grads_wrt_params_dict=dict(zip(keys, grads)),
                                                         num_step=num_step)
-            if msl:
-                parts, preds = target_pass(W, num_step)
-                task_terms.append(importance[num_step] * parts['total'])
-                for k, v in parts.items():
-                    for t in range(T):
-                        logs[t].append((k, v[t]))
-        if not training_phase:
-            with torch.no_grad():
-                parts, preds = target_pass(W, num_steps)
-        elif not msl:
-            parts, preds = target_pass(W, num_steps)
-        if not training_phase or not msl:
-            task_terms.append(parts['total'])
-            for k, v in parts.items():
-                for t in range(T):
-                    logs[t].append((k, v[t]))
+            target(num_step + 1, W)
         if sup_kw:
             self.net.replay_running_stats(sup_kw['front'], tgt_kw['front'], T, self._front_passes(num_steps, msl, training_phase))
-        per_task = torch.stack(task_terms, 0).sum(0)                            # [T]
+        results = self._group_results(frames, ids, torch.stack(task_terms, 0).sum(0), state['preds'], logs, do_evaluation)
+        if not training_phase:
+            self.net.restore_backup_stats()
+        return results
+
+    def _group_results(self, frames, ids, per_task, preds, logs, do_evaluation):
+        """The result dicts of a group of tasks from its per-task losses [T], predictions [T,3,H,W] and per task a list of (loss
+        part, value); PSNR / SSIM of the T tasks in one call."""
         preds = preds.detach()
-        results = []
-        if do_evaluation:          # the T tasks in one call
+        if do_evaluation:
             mse, ssim = self._eval_metrics(preds, frames[self.target_idxs[1]][list(ids)])
-        for t, task_id in enumerate(ids):
+        results = []
+        for t in range(len(ids)):
             res = {'pred': self._to_unit_range(preds[t]).unsqueeze(0), 'logs': logs[t], 'loss': per_task[t]}
             if do_evaluation:
                 res['mse'], res['ssim'] = mse[t], ssim[t]
             results.append(res)
-        if not training_phase:
-            self.net.restore_backup_stats()
         return results
+
+    def _collect(self, num_tasks, local, results, importance, training_phase):
+        """Fold the local tasks' results into what forward() returns, (losses, per-task predictions, metrics), and hand what is
+        logged to _logging."""
+        total_losses, eval_mse, eval_ssim = [], [], []
+        deferred = _DeferredMeters()
+        preds = [[] for _ in range(num_tasks)]
+        for task_id, res in zip(local, results):
+            total_losses.append(res['loss'])
+            preds[task_id] = res['pred']
+            for k, v in res['logs']:
+                deferred.add(k, v)
+            if 'mse' in res:
+                eval_mse.append(res['mse'])
+                eval_ssim.append(res['ssim'])
+        # mean over the GLOBAL meta-batch: local sum / B (the all-reduce of grads completes the mean)
+        local_sum = torch.sum(torch.stack(total_losses)) if total_losses else torch.zeros((), device=self.device)
+        losses = {'loss': local_sum / num_tasks}
+        metrics = {'psnr': utils.AverageMeter(), 'ssim': utils.AverageMeter()}
+        self._logging(losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase)
+        return losses, preds, metrics
 
     def _run_tasks(self, local, body, flatten=None, streams=None):
         """Results of body(task) for the local tasks, in order.  With --task_streams N > 1 on a GPU the tasks are spread
@@ -694,10 +713,6 @@ class SceneAdaptiveInterpolation(nn.Module):
         msl = bool(use_multi_step_loss_optimization and training_phase
                    and epoch < self.args.multi_step_loss_num_epochs)
 
-        total_losses = []
-        deferred = _DeferredMeters()
-        eval_mse, eval_ssim = [], []
-        preds = [[] for _ in range(num_tasks)]
         self.net.zero_grad()
         importance = self.get_per_step_loss_importance_vector()
 
@@ -718,25 +733,7 @@ class SceneAdaptiveInterpolation(nn.Module):
             results = [res for p_ in packed for res in p_['group']]
         else:
             results = self._run_tasks(local, body)
-        for task_id, res in zip(local, results):
-            total_losses.append(res['loss'])
-            preds[task_id] = res['pred']
-            for k, v in res['logs']:
-                deferred.add(k, v)
-            if do_evaluation:
-                eval_mse.append(res['mse'])
-                eval_ssim.append(res['ssim'])
-
-        # mean over the GLOBAL meta-batch: local sum / B (the all-reduce of grads completes the mean)
-        if total_losses:
-            local_sum = torch.sum(torch.stack(total_losses))
-        else:
-            local_sum = torch.zeros((), device=self.device)
-        losses = {'loss': local_sum / num_tasks}
-
-        metrics = {'psnr': utils.AverageMeter(), 'ssim': utils.AverageMeter()}
-        self._logging(losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase)
-        return losses, preds, metrics
+        return self._collect(num_tasks, local, results, importance, training_phase)
 
     def _wants_graphs(self, frames, training_phase):
         """--graph_inner_loop 1: always (where supported); -1 (default): when this rank would otherwise adapt its tasks ONE AT A
@@ -832,7 +829,6 @@ class SceneAdaptiveInterpolation(nn.Module):
         def loop_for(i, T):
             k = key + (i, T)
             if k not in self._graphs:
-                import gc
                 # a graph set pins its static buffers and memory pool: keep the most recently used ones only (evaluation over
                 # clips of many different sizes would otherwise capture, and keep, one set per size) -- but never one this
                 # call still needs (more task streams than MAX_GRAPH_SETS / 2 would otherwise evict their own sets)
@@ -856,18 +852,7 @@ class SceneAdaptiveInterpolation(nn.Module):
         def body(group):
             i = owner[tuple(group)]
             task_losses, preds_g, logs_g = loops[tuple(group)].run_tasks(frames, list(group), importance, accums[i])
-            out = []
-            if do_evaluation:
-                mse, ssim = self._eval_metrics(torch.stack([preds_g[t] for t in range(len(group))]),
-                                               frames[self.target_idxs[1]][list(group)])
-            for t, task_id in enumerate(group):
-                pred = preds_g[t]
-                res = {'loss': task_losses[t], 'pred': self._to_unit_range(pred).unsqueeze(0),
-                       'logs': [(k, v) for parts in logs_g[t] for k, v in parts.items()]}
-                if do_evaluation:
-                    res['mse'], res['ssim'] = mse[t], ssim[t]
-                out.append(res)
-            return out
+            return self._group_results(frames, group, task_losses, preds_g, logs_g, do_evaluation)
 
         if n == 1:
             grouped = [body(g) for g in groups]
@@ -884,24 +869,11 @@ class SceneAdaptiveInterpolation(nn.Module):
         for other in accums[1:]:
             if other is not None:
                 accum.merge(other)
-        deferred = _DeferredMeters()
-        eval_mse, eval_ssim, total_losses = [], [], []
-        preds = [[] for _ in range(num_tasks)]
-        for task_id, res in zip(local, results):
-            total_losses.append(res['loss'])
-            preds[task_id] = res['pred']
-            for k, v in res['logs']:
-                deferred.add(k, v)
-            if do_evaluation:
-                eval_mse.append(res['mse'])
-                eval_ssim.append(res['ssim'])
-        local_sum = torch.sum(torch.stack(total_losses)) if total_losses else torch.zeros((), device=self.device)
-        losses = {'loss': (local_sum / num_tasks).detach()}
+        losses, preds, metrics = self._collect(num_tasks, local, results, importance, training_phase)
+        losses['loss'] = losses['loss'].detach()
         if training_phase:
             accum.num_tasks = num_tasks
             self._manual_grads = accum
-        metrics = {'psnr': utils.AverageMeter(), 'ssim': utils.AverageMeter()}
-        self._logging(losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase)
         return losses, preds, metrics
 
     def _reduce_logging(self, losses, meters, metrics):
@@ -967,7 +939,7 @@ class SceneAdaptiveInterpolation(nn.Module):
         if self.device.type == 'cuda' and self._ws_kernels_in_use() and _hip.ws_armed():
             # Fail closed: a bounded wait of the wave-specialised SepConv kernels that gave up (csrc/sepconv_ws.hip) has produced wrong
             # gradients.  The stream is drained HERE, before theta moves -- one host wait per meta-iteration, ~0.3 % of a C2 iteration
-            # (profiles/r06_ws_check_cost.txt) -- and the exception leaves theta, the optimizer state and the scheduler untouched.
+            # (a figure no kept artefact backs) -- and the exception leaves theta, the optimizer state and the scheduler untouched.
             torch.cuda.current_stream(self.device).synchronize()
             _hip.ws_check("this meta-iteration at epoch %d: its outer step was NOT applied" % self.current_epoch)
         self.optimizer.step()
@@ -1030,11 +1002,10 @@ class SceneAdaptiveInterpolation(nn.Module):
                 steps = self.args.number_of_evaluation_steps_per_iter
                 weights = self._adapt(frames, task_id, steps, False, fronts={} if hasattr(self.net, 'front') else None)
                 with torch.no_grad():
-                    out = self.net.forward(frames[1][task_id].unsqueeze(0), frames[2][task_id].unsqueeze(0),
-                                           params=weights, backup_running_statistics=False,
-                                           num_step=max(steps - 1, 0))
-                if isinstance(out, tuple):     # superslomo (:686-688)
-                    out = self.revNormalize(out[0].squeeze(0)).unsqueeze(0)
+                    out, extras = self._run_pass(frames[1][task_id].unsqueeze(0), frames[2][task_id].unsqueeze(0), weights,
+                                                 max(steps - 1, 0), support=False, extras=True)
+                if extras is not None:         # superslomo (:686-688)
+                    out = self.revNormalize(out.squeeze(0)).unsqueeze(0)
                 preds[task_id] = out.squeeze(0).detach()
                 self.net.restore_backup_stats()
         finally:
