@@ -22,6 +22,7 @@
  *   savfi_l1_mse_f32           nn.L1Loss / nn.MSELoss                 loss.py:287-290
  *   savfi_ssim_loss_f32        pytorch_msssim.SSIM as Loss constructs it, forward and gradient   loss.py:294, pytorch_msssim/__init__.py:7-131
  *   savfi_psnr_ssim_f32        utils.quantize + calc_psnr's squared error + ssim(val_range=255), `rows` image pairs per call   utils.py:171-204, pytorch_msssim/__init__.py:19-75
+ *   savfi_msssim_f32 / _bwd_f32  pytorch_msssim.msssim as implemented (five levels, per-level range rule), forward and gradient   pytorch_msssim/__init__.py:78-104
  *   savfi_upsample2x_fwd/bwd_f32  bilinear x2 up-sampling                 sepconv/model.py:191,213-234; voxel_flow.py:400-414
  *   savfi_upsample2x_window_fwd/bwd_f32  the same map on a window (SepConv Subnets on the frame area)  sepconv/model.py:309-349
  *   savfi_bias_act_fwd/bwd_f32 conv bias add + (Leaky)ReLU and their backward + bias gradient
@@ -78,7 +79,8 @@ extern "C" {
  * savfi_pwcwarp_fwd_f32; then, for DAIN's frozen front and rectify net, savfi_bn_stats_scratch_floats, savfi_bn_stats_f32,
  * savfi_bn_apply_relu_f32, savfi_bn_running_update_f32, savfi_maxpool2x2_f32, savfi_upnearest2x_add_f32, savfi_add_relu_f32,
  * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32; then savfi_conv3x3_f4_launched_workgroups, savfi_conv3x3_debug_f4_block_decode,
- * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32. */
+ * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32; then, for multi-scale
+ * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -363,6 +365,37 @@ int savfi_ssim_loss_bwd_f32(const float* sr, const float* hr, const float* g_los
 int64_t savfi_psnr_ssim_scratch_bytes(int rows, int C, int H, int W);
 int savfi_psnr_ssim_f32(const float* pred, const float* target, float* result, unsigned long long* sq_sum, void* scratch,
                         int rows, int C, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Multi-scale SSIM and its gradient (csrc/ssim.hip; pytorch_msssim/__init__.py:78-104 "as implemented"), added under ABI 24.
+ *   img1, img2 [rows, C, H, W] (prediction, target).  Five levels s = 0..4 on H >> s x W >> s images: the SSIM map and the map
+ *   cs = v1 / v2 under the valid window of min(11, H_s, W_s) taps of gaussian(n, 1.5) centred at n / 2, then both images 2 x 2
+ *   averaged (floor: an odd last row / column is dropped).  With the fp32 weights w = 0.0448, 0.2856, 0.3001, 0.2363, 0.1333
+ *     result[r] = mean(ssim_4) ^ (4 w_4) * prod_{s < 4} mean(cs_s) ^ w_s        (the reference's prod(pow1[:-1] * pow2[-1])),
+ *   normalize != 0: every mean m replaced by (m + 1) / 2 first.  A negative base gives NaN, as the reference does.
+ *   The reference pools once more after the fifth level and so raises below 32: H, W >= 32, SAVFI_E_SHAPE otherwise;
+ *   rows * C <= 65535 and H * W < 2^31, SAVFI_E_TOOBIG otherwise.
+ *   range_mode: the modes of savfi_ssim_loss_f32.  Without a fixed class the range rule is applied AGAIN ON EVERY LEVEL to that
+ *   level's (pooled) prediction, per row (PER_ROW) or over everything (BATCH: one value, means over the whole batch, result and
+ *   g_out have one element); FIXED + k holds on every level.
+ *   quantize != 0: both images are quantised as savfi_psnr_ssim_f32 does while level 0 loads them (unit-range inputs; forward only;
+ *   with FIXED + 2 this is msssim(quantize(pred), quantize(target), val_range=255)); nothing quantised is written.
+ *   One launch per level (partial sums of both maps, the pooled pair of the next level and the partial extrema of its prediction)
+ *   and a finish; plus the range pass of level 0 without a fixed class.  No atomics, no cleared memory, no host read: capturable
+ *   and bit-reproducible.
+ *   `scratch`: savfi_msssim_scratch_bytes(rows, C, H, W) bytes, 16-byte aligned, caller-owned, the same for every mode.  It starts
+ *   with 16 32-bit words per result row (per row of the batch in PER_ROW / FIXED, one row in BATCH): float d result / d mean(ssim_s),
+ *   s = 0..4 (zero for s < 4), float d result / d mean(cs_s) (zero for s = 4), uint32 range class of level s = 0..4, one spare.
+ *   Then the pooled pairs, the gradients of the pooled predictions, partial sums and partial extrema.
+ *   bwd: call with the forward's arguments and its scratch untouched.  g_img1 [rows, C, H, W] = g_out[r] * d result[r] / d img1,
+ *   fully overwritten, coarse to fine with one launch per level: the level's own map gradient plus a quarter of the next-coarser
+ *   level's, replicated (zero where the floor dropped a row / column).  img2 gets no gradient.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_msssim_scratch_bytes(int rows, int C, int H, int W);
+int savfi_msssim_f32(const float* img1, const float* img2, float* result, void* scratch, int rows, int C, int H, int W,
+                     int range_mode, int normalize, int quantize, void* stream);
+int savfi_msssim_bwd_f32(const float* img1, const float* img2, const float* g_out, void* scratch, float* g_img1, int rows,
+                         int C, int H, int W, int range_mode, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:

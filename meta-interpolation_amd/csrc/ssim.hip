@@ -22,6 +22,9 @@
 //                  pass, no range word), and next to the SSIM partial sum the integer sum of squared differences of the pixels the
 //                  workgroup owns
 //   metric_finish  per row: SSIM partial sums in ssim_finish's order -> mean; integer partials as 64 bits -> S, mse = S / (65025 n)
+// Multi-scale SSIM (pytorch_msssim/__init__.py:78-104) is both tiles once more, per level: msssim_level (forward tile + 2 x 2 pooling of the
+// next level's pair + partial extrema of its prediction), msssim_finish (means, product, factors), msssim_bwd_level (coarse to fine); see
+// the section further down.
 // Every window sum is accumulated tap 0 .. 10 in the same association for every pixel, whatever its place in a tile.
 // LDS: lanes run along image columns in every pass, so each ds_read_b32 / ds_write_b32 of a wave touches consecutive
 // words (conflict-free for any row stride); 49 KB (forward) and 59 KB (backward) of static LDS: three resp. two workgroups per CU.
@@ -189,6 +192,7 @@ constexpr unsigned SQ_NAN = 0xffffffffu;
 // (q_p - q_t)^2 as an integer over the pixels it owns -> sq_partial (same index).  Every pixel of the plane has one owner: the
 // tiles step over the SSIM positions, so the last tile row / column also own the 10 trailing pixel rows / columns, which lie
 // inside their patch (<= 26 x 74 pixels * 65025 < 2^27: the 32-bit sum is exact).  A NaN among the owned pixels -> SQ_NAN.
+// msssim_level below is a second copy of this tile (and row_taps_n of row_taps): a fix here has to be made there too.
 template <bool METRIC>
 __device__ __forceinline__ void fwd_tile(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
                                          int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word, float* __restrict__ partial,
@@ -334,7 +338,7 @@ __global__ __launch_bounds__(64) void metric_finish(const float* __restrict__ pa
   }
 }
 
-// grid (cdiv(W, BW), cdiv(H, BH), rows * C)
+// grid (cdiv(W, BW), cdiv(H, BH), rows * C).  msssim_bwd_level below is a second copy of this kernel: a fix here has to be made there too.
 __global__ __launch_bounds__(NT) void ssim_bwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ g_loss,
                                                const unsigned* __restrict__ range_word, float* __restrict__ g_sr, int C, int H, int W,
                                                float inv_2n, int vec_ok) {
@@ -429,6 +433,366 @@ __global__ __launch_bounds__(NT) void ssim_bwd(const float* __restrict__ sr, con
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Multi-scale SSIM (pytorch_msssim/__init__.py:78-104, "as implemented"): five levels, each the SSIM map and the cs map v1 / v2 of
+// one image pair under the window of min(11, H_s, W_s) taps, then both images 2 x 2 averaged (floor).  Result
+// ssim_4 ^ (4 w_4) * prod_{s < 4} cs_s ^ w_s (the reference's prod(pow1[:-1] * pow2[-1])).
+//   msssim_level   the forward tile once more: SSIM and cs partial sums of one level, and out of the same LDS patches the 2 x 2
+//                  averages of the pixels the workgroup owns (both images, the next level's operands) and the partial extrema of
+//                  the pooled prediction (the next level's range class: the pooled pair is not read again for it)
+//   msssim_finish  per row: the ten means (partial sums in a fixed order), the result, and the ten factors d out / d mean
+//   msssim_bwd_level  coarse to fine, ssim_bwd once more: the level's own map gradient (cs map on levels 0 .. 3, SSIM map on level 4:
+//                  the other factors are identically zero) plus a quarter of the next-coarser level's gradient, replicated
+// A window of n < 11 taps is the table row below, zero beyond tap n - 1: every pass still runs 11 taps in ssim_fwd's association
+// (the n = 11 row is G), the trailing products are 0 * (a pixel or the zero fill), and the valid positions are H - n + 1, W - n + 1.
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int MS_LEVELS = 5;
+constexpr int MS_HEAD = 16;      // 32-bit words per row at the start of the scratch: 10 factors, 5 class words, 1 spare
+
+// gaussian(n, 1.5) of pytorch_msssim for n = 1 .. 11: exp(-(i - n / 2)^2 / 4.5) in double, rounded to fp32, divided by the fp32 sum
+__device__ __constant__ float GN[WIN][WIN] = {
+    {0x1p+0f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.c75814p-2f, 0x1.1c53f6p-1f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.3b3046p-2f, 0x1.899f76p-2f, 0x1.3b3046p-2f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.177ae4p-3f, 0x1.102d28p-2f, 0x1.53e83ep-2f, 0x1.102d28p-2f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.ebd74ep-4f, 0x1.defcdep-3f, 0x1.2b1778p-2f, 0x1.defcdep-3f, 0x1.ebd74ep-4f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.3781f8p-5f, 0x1.d9236ep-4f, 0x1.ccc61cp-3f, 0x1.1fb7eep-2f, 0x1.ccc61cp-3f, 0x1.d9236ep-4f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.2c18a6p-5f, 0x1.c7ce56p-4f, 0x1.bbe4fap-3f, 0x1.152db4p-2f, 0x1.bbe4fap-3f, 0x1.c7ce56p-4f, 0x1.2c18a6p-5f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.f6d8f2p-8f, 0x1.29cb2ep-5f, 0x1.c44f04p-4f, 0x1.b87d0cp-3f, 0x1.130d42p-2f, 0x1.b87d0cp-3f, 0x1.c44f04p-4f, 0x1.29cb2ep-5f, 0.f, 0.f,
+     0.f},
+    {0x1.f304c2p-8f, 0x1.2786b2p-5f, 0x1.c0dd56p-4f, 0x1.b5226ap-3f, 0x1.10f51ap-2f, 0x1.b5226ap-3f, 0x1.c0dd56p-4f, 0x1.2786b2p-5f,
+     0x1.f304c2p-8f, 0.f, 0.f},
+    {0x1.0ddc78p-10f, 0x1.f2813ep-8f, 0x1.2738dp-5f, 0x1.c0670ap-4f, 0x1.b4af36p-3f, 0x1.10ad2ap-2f, 0x1.b4af36p-3f, 0x1.c0670ap-4f,
+     0x1.2738dp-5f, 0x1.f2813ep-8f, 0.f},
+    {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f, 0x1.b43c3ep-3f, 0x1.bff0fep-4f,
+     0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f}};
+
+__device__ __forceinline__ void row_taps_n(const float (&g)[WIN], const float* __restrict__ x, const float* __restrict__ y, float (&s)[5]) {
+  s[0] = s[1] = s[2] = s[3] = s[4] = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIN; ++k) {
+    const float a = x[k], b = y[k];
+    s[0] = fmaf(g[k], a, s[0]);
+    s[1] = fmaf(g[k], b, s[1]);
+    s[2] = fmaf(g[k], a * a, s[2]);
+    s[3] = fmaf(g[k], b * b, s[3]);
+    s[4] = fmaf(g[k], a * b, s[4]);
+  }
+}
+
+// One level's forward tile.  grid (tiles_x, tiles_y, rows * C) over the (H - n + 1) x (W - n + 1) positions; the workgroup's index
+// w = (z * tiles_y + by) * tiles_x + bx.  partial[w] = SSIM sum, partial[total + w] = cs sum.  ext: the partial extrema of this
+// level's prediction, ext_blocks (max, min) pairs per row (ssim_range's on level 0, the previous level's workgroups' after that).
+// pool1 / pool2 (NULL on the last level): [rows * C, H / 2, W / 2] averages, ((a + b) + c) + d over (0,0) (0,1) (1,0) (1,1), times
+// 0.25 -- avg_pool2d's order; ext_out[2 w] = max, min of the pooled prediction values this workgroup wrote.  Pixel ownership is
+// metric_tile's: TH and TW are even, so no 2 x 2 block straddles two owners.
+// SECOND COPY: the staging, the row and column passes and the map arithmetic restate fwd_tile (and row_taps_n restates row_taps)
+// rather than sharing code with it, so that the single-scale kernels keep their bits.  A fix to the tile has to be made in both places.
+template <bool QUANT>
+__global__ __launch_bounds__(NT) void msssim_level(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
+                                                   int ext_blocks, int fixed_cls, unsigned* __restrict__ head, int level,
+                                                   float* __restrict__ partial, float* __restrict__ pool1, float* __restrict__ pool2,
+                                                   float* __restrict__ ext_out, int C, int H, int W, int taps, int vec_ok) {
+  __shared__ __attribute__((aligned(16))) float px[PH * PW];
+  __shared__ __attribute__((aligned(16))) float py[PH * PW];
+  __shared__ float rf[5][PH][TW];
+  __shared__ float red[2 * NW];
+  const int z = blockIdx.z, row = z / C;
+  const int y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
+  const int Ho = H - taps + 1, Wo = W - taps + 1;
+  const size_t plane = (size_t)z * H * W;
+  const size_t wg = ((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  const size_t wgs = (size_t)gridDim.z * gridDim.y * gridDim.x;
+  load_patch<PH, PW, QUANT>(sr + plane, px, y0, x0, H, W, vec_ok);
+  load_patch<PH, PW, QUANT>(hr + plane, py, y0, x0, H, W, vec_ok);
+  unsigned cls = (unsigned)fixed_cls;
+  if (fixed_cls < 0) {
+    float hi = -INFINITY, lo = INFINITY;
+    const float* e = ext + (size_t)row * ext_blocks * 2;
+    for (int i = threadIdx.x; i < ext_blocks; i += NT) {
+      hi = fmaxf(hi, e[2 * i]);
+      lo = fminf(lo, e[2 * i + 1]);
+    }
+    block_extrema(hi, lo, red);
+    cls = (lo < -0.5f ? 1u : 0u) | (hi > 128.f ? 2u : 0u);
+  }
+  if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && z == row * C) head[(size_t)row * MS_HEAD + 2 * MS_LEVELS + level] = cls;
+  float C1, C2;
+  ssim_constants(cls, C1, C2);
+  float g[WIN];
+#pragma unroll
+  for (int k = 0; k < WIN; ++k) g[k] = GN[taps - 1][k];
+  __syncthreads();
+
+  if (pool1) {
+    const int own_h = blockIdx.y + 1 == gridDim.y ? H - y0 : TH, own_w = blockIdx.x + 1 == gridDim.x ? W - x0 : TW;
+    const int ph = own_h / 2, pw = own_w / 2, H2 = H / 2, W2 = W / 2;
+    const size_t pplane = (size_t)z * H2 * W2;
+    float hi = -INFINITY, lo = INFINITY;
+    for (int i = threadIdx.x; i < ph * pw; i += NT) {
+      const int r = i / pw, c = i - r * pw;
+      const float* a = px + (2 * r) * PW + 2 * c;
+      const float* b = py + (2 * r) * PW + 2 * c;
+      const float va = (((a[0] + a[1]) + a[PW]) + a[PW + 1]) * 0.25f;
+      const float vb = (((b[0] + b[1]) + b[PW]) + b[PW + 1]) * 0.25f;
+      const size_t o = pplane + (size_t)(y0 / 2 + r) * W2 + (x0 / 2 + c);
+      pool1[o] = va;
+      pool2[o] = vb;
+      hi = fmaxf(hi, va);
+      lo = fminf(lo, va);
+    }
+    block_extrema(hi, lo, red);
+    if (threadIdx.x == 0) {
+      ext_out[2 * wg] = hi;
+      ext_out[2 * wg + 1] = lo;
+    }
+  }
+
+  for (int i = threadIdx.x; i < PH * TW; i += NT) {
+    const int r = i / TW, c = i - r * TW;
+    float s[5];
+    row_taps_n(g, px + r * PW + c, py + r * PW + c, s);
+#pragma unroll
+    for (int p = 0; p < 5; ++p) rf[p][r][c] = s[p];
+  }
+  __syncthreads();
+
+  const int c = threadIdx.x & (TW - 1), r0 = (threadIdx.x / TW) * 4;
+  float mom[4][5];
+#pragma unroll
+  for (int p = 0; p < 5; ++p) {
+    float v[4 + HALO];
+#pragma unroll
+    for (int k = 0; k < 4 + HALO; ++k) v[k] = rf[p][r0 + k][c];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], v[o + k], acc);
+      mom[o][p] = acc;
+    }
+  }
+  float sum = 0.f, cs = 0.f;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    float r1, r2, B1, B2;
+    const float v = ssim_value(mom[o], C1, C2, r1, r2, B1, B2);
+    if (y0 + r0 + o < Ho && x0 + c < Wo) {
+      sum += v;
+      cs += r2;
+    }
+  }
+  const float tot = block_sum<NW>(sum, red);
+  const float tcs = block_sum<NW>(cs, red);
+  if (threadIdx.x == 0) {
+    partial[wg] = tot;
+    partial[wgs + wg] = tcs;
+  }
+}
+
+struct MsFinish {
+  long long partial[MS_LEVELS];      // offset of the level's partial sums in the scratch, floats
+  int blocks[MS_LEVELS];             // workgroups per row
+  int wgs[MS_LEVELS];                // workgroups of the level (the cs sums follow the SSIM sums)
+  float n[MS_LEVELS];                // map values per row
+};
+
+// One workgroup per row.  The ten means as ssim_finish adds them (fp32, / n), the normalisation (m + 1) / 2 in fp32 as the reference
+// does it; powers and factors in double by one thread.  head[row]: d out / d ssim_0..4 (only ssim_4's is non-zero), d out / d cs_0..4
+// (cs_4's is zero), with respect to the plain means.  A negative base: pow gives NaN, and so are the result and every factor.
+__global__ __launch_bounds__(64) void msssim_finish(const float* __restrict__ scratch, float* __restrict__ head, float* __restrict__ result,
+                                                    MsFinish f, int normalize) {
+  const float w[MS_LEVELS] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
+  const int row = blockIdx.x;
+  float ms[MS_LEVELS], mc[MS_LEVELS];
+#pragma unroll
+  for (int s = 0; s < MS_LEVELS; ++s) {
+    const float* p = scratch + f.partial[s] + (size_t)row * f.blocks[s];
+    float a = 0.f, b = 0.f;
+    for (int i = threadIdx.x; i < f.blocks[s]; i += 64) {
+      a += p[i];
+      b += p[f.wgs[s] + i];
+    }
+    ms[s] = wave_sum(a) / f.n[s];
+    mc[s] = wave_sum(b) / f.n[s];
+    if (normalize) {
+      ms[s] = (ms[s] + 1.f) / 2.f;
+      mc[s] = (mc[s] + 1.f) / 2.f;
+    }
+  }
+  if (threadIdx.x != 0) return;
+  const double w4 = 4.0 * (double)w[MS_LEVELS - 1];
+  double out = pow((double)ms[MS_LEVELS - 1], w4);
+#pragma unroll
+  for (int s = 0; s < MS_LEVELS - 1; ++s) out *= pow((double)mc[s], (double)w[s]);
+  const double chain = normalize ? 0.5 : 1.0;
+  float* h = head + (size_t)row * MS_HEAD;
+#pragma unroll
+  for (int s = 0; s < MS_LEVELS - 1; ++s) {
+    h[s] = 0.f;
+    h[MS_LEVELS + s] = (float)(chain * out * (double)w[s] / (double)mc[s]);
+  }
+  h[MS_LEVELS - 1] = (float)(chain * out * w4 / (double)ms[MS_LEVELS - 1]);
+  h[2 * MS_LEVELS - 1] = 0.f;
+  result[row] = (float)out;
+}
+
+// One level of the backward.  grid (cdiv(W, BW), cdiv(H, BH), rows * C).  SSIM_TERM: the SSIM map's gradient times
+// d out / d ssim_level (the last level), else the cs map's times d out / d cs_level.  g_coarse (NULL on the last level): the gradient
+// of the next-coarser level [rows * C, H / 2, W / 2]; a pixel whose 2 x 2 block was dropped by the floor gets nothing from it.
+// SECOND COPY: the moments, the map's partial derivatives and the transposed window passes restate ssim_bwd, for the same reason as
+// msssim_level restates fwd_tile.  A fix to the backward tile has to be made in both places.
+template <bool SSIM_TERM>
+__global__ __launch_bounds__(NT) void msssim_bwd_level(const float* __restrict__ sr, const float* __restrict__ hr,
+                                                       const float* __restrict__ g_out, const float* __restrict__ head, int level,
+                                                       const float* __restrict__ g_coarse, float* __restrict__ g_sr, int C, int H, int W,
+                                                       int taps, float inv_n, int vec_ok) {
+  __shared__ __attribute__((aligned(16))) float px[QH * QW];
+  __shared__ __attribute__((aligned(16))) float py[QH * QW];
+  __shared__ float rf[5][QH][CW];
+  __shared__ float coef[3][CH][CW];
+  float(*ar)[CH][BW] = reinterpret_cast<float(*)[CH][BW]>(&rf[0][0][0]);
+  const int z = blockIdx.z, row = z / C;
+  const int y0 = blockIdx.y * BH, x0 = blockIdx.x * BW;
+  const int Ho = H - taps + 1, Wo = W - taps + 1;
+  const size_t plane = (size_t)z * H * W;
+  load_patch<QH, QW>(sr + plane, px, y0 - HALO, x0 - QX, H, W, vec_ok);
+  load_patch<QH, QW>(hr + plane, py, y0 - HALO, x0 - QX, H, W, vec_ok);
+  const float* h = head + (size_t)row * MS_HEAD;
+  float C1, C2;
+  ssim_constants(reinterpret_cast<const unsigned*>(h)[2 * MS_LEVELS + level], C1, C2);
+  float g[WIN];
+#pragma unroll
+  for (int k = 0; k < WIN; ++k) g[k] = GN[taps - 1][k];
+  __syncthreads();
+
+  for (int i = threadIdx.x; i < QH * CW; i += NT) {
+    const int r = i / CW, cc = i - r * CW;
+    float s[5];
+    row_taps_n(g, px + r * QW + cc + (QX - HALO), py + r * QW + cc + (QX - HALO), s);
+#pragma unroll
+    for (int p = 0; p < 5; ++p) rf[p][r][cc] = s[p];
+  }
+  __syncthreads();
+
+  for (int i = threadIdx.x; i < CH * CW; i += NT) {
+    const int cr = i / CW, cc = i - cr * CW;
+    const int oy = y0 - HALO + cr, ox = x0 - HALO + cc;
+    float a = 0.f, b = 0.f, c = 0.f;
+    if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
+      float m[5];
+#pragma unroll
+      for (int p = 0; p < 5; ++p) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], rf[p][cr + k][cc], acc);
+        m[p] = acc;
+      }
+      float r1, r2, B1, B2;
+      const float v = ssim_value(m, C1, C2, r1, r2, B1, B2);
+      {
+#pragma clang fp contract(off)
+        if constexpr (SSIM_TERM) {
+          b = -v / B2;
+          c = (2.f * r1) / B2;
+          const float dm = ((2.f * m[1]) * r2) / B1 - ((2.f * m[0]) * v) / B1;
+          a = (dm - (2.f * m[0]) * b) - m[1] * c;
+        } else {
+          // cs = A2 / B2 does not see mu1 but through s1 and s12; an identical pair gives r2 = 1, c == -2 b and a == 0 exactly
+          b = -r2 / B2;
+          c = 2.f / B2;
+          a = (0.f - (2.f * m[0]) * b) - m[1] * c;
+        }
+      }
+    }
+    coef[0][cr][cc] = a;
+    coef[1][cr][cc] = b;
+    coef[2][cr][cc] = c;
+  }
+  __syncthreads();
+
+  for (int i = threadIdx.x; i < CH * BW; i += NT) {
+    const int cr = i / BW, ix = i - cr * BW;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], coef[p][cr][ix + HALO - k], acc);
+      ar[p][cr][ix] = acc;
+    }
+  }
+  __syncthreads();
+
+  const float scale = (g_out[row] * h[SSIM_TERM ? level : MS_LEVELS + level]) * inv_n;
+  const int H2 = H / 2, W2 = W / 2;
+  for (int i = threadIdx.x; i < BH * BW; i += NT) {
+    const int iy = i / BW, ix = i - iy * BW;
+    const int gy = y0 + iy, gx = x0 + ix;
+    float t[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], ar[p][iy + HALO - k][ix], acc);
+      t[p] = acc;
+    }
+    if (gy < H && gx < W) {
+#pragma clang fp contract(off)
+      const float x = px[(iy + HALO) * QW + ix + QX], y = py[(iy + HALO) * QW + ix + QX];
+      float v = scale * ((t[0] + (2.f * x) * t[1]) + y * t[2]);
+      if (g_coarse && (gy >> 1) < H2 && (gx >> 1) < W2) v += 0.25f * g_coarse[(size_t)z * H2 * W2 + (size_t)(gy >> 1) * W2 + (gx >> 1)];
+      g_sr[plane + (size_t)gy * W + gx] = v;
+    }
+  }
+}
+
+// NULL, then SHAPE, UNSUPPORTED, TOOBIG.  The reference pools once more after the fifth level: 32 is the smallest legal size.
+int msssim_check(int rows, int C, int H, int W, int range_mode) {
+  if (rows <= 0 || C <= 0 || H < 32 || W < 32) return SAVFI_E_SHAPE;
+  if (range_mode < 0 || range_mode > SAVFI_SSIM_RANGE_FIXED + 3) return SAVFI_E_UNSUPPORTED;
+  if ((int64_t)rows * C > 65535 || (int64_t)H * W > 0x7fffffffLL) return SAVFI_E_TOOBIG;      // ssim_check's limits
+  return SAVFI_OK;
+}
+
+// Where everything lies in the scratch, in 32-bit words (every region starts on a multiple of four words).  The same for every range mode.
+struct MsPlan {
+  int h[MS_LEVELS], w[MS_LEVELS], taps[MS_LEVELS], tx[MS_LEVELS], ty[MS_LEVELS];
+  int64_t img1[MS_LEVELS], img2[MS_LEVELS], grad[MS_LEVELS];      // levels 1 .. 4
+  int64_t partial[MS_LEVELS], ext[MS_LEVELS];
+  int64_t words;
+};
+
+MsPlan msssim_plan(int rows, int C, int H, int W) {
+  MsPlan p;
+  const int64_t planes = (int64_t)rows * C;
+  auto up4 = [](int64_t v) { return (v + 3) & ~(int64_t)3; };
+  int64_t at = up4((int64_t)rows * MS_HEAD);
+  for (int s = 0; s < MS_LEVELS; ++s) {
+    p.h[s] = H >> s;
+    p.w[s] = W >> s;
+    p.taps[s] = p.h[s] < WIN || p.w[s] < WIN ? (p.h[s] < p.w[s] ? p.h[s] : p.w[s]) : WIN;
+    p.tx[s] = savfi_cdiv(p.w[s] - p.taps[s] + 1, TW);
+    p.ty[s] = savfi_cdiv(p.h[s] - p.taps[s] + 1, TH);
+  }
+  for (int s = 1; s < MS_LEVELS; ++s) {
+    const int64_t n = up4(planes * p.h[s] * p.w[s]);
+    p.img1[s] = at;
+    p.img2[s] = at + n;
+    p.grad[s] = at + 2 * n;
+    at += 3 * n;
+  }
+  for (int s = 0; s < MS_LEVELS; ++s) {
+    p.partial[s] = at;
+    at += up4(2 * planes * p.tx[s] * p.ty[s]);
+  }
+  for (int s = 0; s < MS_LEVELS; ++s) {
+    p.ext[s] = at;
+    at += up4(s == 0 ? 2 * (int64_t)rows * RANGE_MAX_BLOCKS : 2 * planes * p.tx[s - 1] * p.ty[s - 1]);
+  }
+  p.words = at;
+  return p;
+}
+
 int ssim_check(int rows, int C, int H, int W) {
   if (rows <= 0 || C <= 0 || H < WIN || W < WIN) return SAVFI_E_SHAPE;
   if ((int64_t)rows * C > 65535 || (int64_t)H * W > 0x7fffffffLL) return SAVFI_E_TOOBIG;      // grid z; in-plane indices are int
@@ -507,4 +871,93 @@ extern "C" int savfi_psnr_ssim_f32(const float* pred, const float* target, float
   hipLaunchKernelGGL(metric_finish, dim3(rows), dim3(64), 0, st, partial, sq_partial, result, sq_sum, C * tx * ty,
                      (float)((int64_t)C * (H - HALO) * (W - HALO)), (double)C * H * W);
   return savfi_launch_status();
+}
+
+extern "C" int64_t savfi_msssim_scratch_bytes(int rows, int C, int H, int W) {
+  if (int e = msssim_check(rows, C, H, W, SAVFI_SSIM_RANGE_PER_ROW)) return e;
+  return msssim_plan(rows, C, H, W).words * (int64_t)sizeof(float);
+}
+
+extern "C" int savfi_msssim_f32(const float* img1, const float* img2, float* result, void* scratch, int rows, int C, int H, int W,
+                                int range_mode, int normalize, int quantize, void* stream) {
+  if (!img1 || !img2 || !result || !scratch) return SAVFI_E_NULL;
+  if (int e = msssim_check(rows, C, H, W, range_mode)) return e;
+  const MsPlan p = msssim_plan(rows, C, H, W);
+  float* base = (float*)scratch;
+  if (range_mode == SAVFI_SSIM_RANGE_BATCH) {      // one value over everything: the samples are further channel planes
+    C *= rows;
+    rows = 1;
+  }
+  const int fixed_cls = range_mode >= SAVFI_SSIM_RANGE_FIXED ? range_mode - SAVFI_SSIM_RANGE_FIXED : -1;
+  hipStream_t st = (hipStream_t)stream;
+  int eb = 0;
+  if (fixed_cls < 0) {
+    const int64_t n = (int64_t)C * H * W;
+    eb = (int)((n + RANGE_PER_BLOCK - 1) / RANGE_PER_BLOCK);
+    if (eb > RANGE_MAX_BLOCKS) eb = RANGE_MAX_BLOCKS;
+    const long long per_block = (((n + eb - 1) / eb) + 3) & ~3LL;
+    const int rvec = (((uintptr_t)img1 & 15u) == 0) && (rows == 1 || n % 4 == 0);
+    hipLaunchKernelGGL(ssim_range, dim3(eb, rows), dim3(NT), 0, st, img1, base + p.ext[0], (long long)n, per_block, rvec);
+    if (int e = savfi_launch_status()) return e;
+  }
+  MsFinish f;
+  const float* x = img1;
+  const float* y = img2;
+  for (int s = 0; s < MS_LEVELS; ++s) {
+    const bool last = s + 1 == MS_LEVELS;
+    const int vec_ok = ((((uintptr_t)x | (uintptr_t)y) & 15u) == 0) && (p.w[s] % 4 == 0);
+    float* o1 = last ? nullptr : base + p.img1[s + 1];
+    float* o2 = last ? nullptr : base + p.img2[s + 1];
+    float* eo = last ? nullptr : base + p.ext[s + 1];
+    const dim3 grid(p.tx[s], p.ty[s], rows * C);
+    if (s == 0 && quantize) {
+      hipLaunchKernelGGL(msssim_level<true>, grid, dim3(NT), 0, st, x, y, base + p.ext[s], eb, fixed_cls, (unsigned*)base, s,
+                         base + p.partial[s], o1, o2, eo, C, p.h[s], p.w[s], p.taps[s], vec_ok);
+    } else {
+      hipLaunchKernelGGL(msssim_level<false>, grid, dim3(NT), 0, st, x, y, base + p.ext[s], eb, fixed_cls, (unsigned*)base, s,
+                         base + p.partial[s], o1, o2, eo, C, p.h[s], p.w[s], p.taps[s], vec_ok);
+    }
+    if (int e = savfi_launch_status()) return e;
+    f.partial[s] = p.partial[s];
+    f.blocks[s] = C * p.tx[s] * p.ty[s];
+    f.wgs[s] = rows * C * p.tx[s] * p.ty[s];
+    f.n[s] = (float)((int64_t)C * (p.h[s] - p.taps[s] + 1) * (p.w[s] - p.taps[s] + 1));
+    eb = f.blocks[s];      // the next level's extrema: one pair per workgroup of this one
+    x = o1;
+    y = o2;
+  }
+  hipLaunchKernelGGL(msssim_finish, dim3(rows), dim3(64), 0, st, base, base, result, f, normalize ? 1 : 0);
+  return savfi_launch_status();
+}
+
+extern "C" int savfi_msssim_bwd_f32(const float* img1, const float* img2, const float* g_out, void* scratch, float* g_img1, int rows,
+                                    int C, int H, int W, int range_mode, void* stream) {
+  if (!img1 || !img2 || !g_out || !scratch || !g_img1) return SAVFI_E_NULL;
+  if (int e = msssim_check(rows, C, H, W, range_mode)) return e;
+  const MsPlan p = msssim_plan(rows, C, H, W);
+  float* base = (float*)scratch;
+  if (range_mode == SAVFI_SSIM_RANGE_BATCH) {
+    C *= rows;
+    rows = 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int s = MS_LEVELS - 1; s >= 0; --s) {
+    const bool last = s + 1 == MS_LEVELS;
+    const float* x = s ? base + p.img1[s] : img1;
+    const float* y = s ? base + p.img2[s] : img2;
+    float* gx = s ? base + p.grad[s] : g_img1;
+    const float* gc = last ? nullptr : base + p.grad[s + 1];
+    const int vec_ok = ((((uintptr_t)x | (uintptr_t)y) & 15u) == 0) && (p.w[s] % 4 == 0);
+    const float inv_n = (float)(1.0 / (double)((int64_t)C * (p.h[s] - p.taps[s] + 1) * (p.w[s] - p.taps[s] + 1)));
+    const dim3 grid(savfi_cdiv(p.w[s], BW), savfi_cdiv(p.h[s], BH), rows * C);
+    if (last) {
+      hipLaunchKernelGGL(msssim_bwd_level<true>, grid, dim3(NT), 0, st, x, y, g_out, base, s, gc, gx, C, p.h[s], p.w[s], p.taps[s], inv_n,
+                         vec_ok);
+    } else {
+      hipLaunchKernelGGL(msssim_bwd_level<false>, grid, dim3(NT), 0, st, x, y, g_out, base, s, gc, gx, C, p.h[s], p.w[s], p.taps[s], inv_n,
+                         vec_ok);
+    }
+    if (int e = savfi_launch_status()) return e;
+  }
+  return SAVFI_OK;
 }

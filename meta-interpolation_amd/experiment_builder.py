@@ -40,6 +40,11 @@ class ExperimentBuilder(object):
         parts += ["{}: {:.4f}".format(k, float(v.avg)) for k, v in metrics.items()]
         return ", ".join(parts)
 
+    @staticmethod
+    def _msssim_suffix(acc):
+        """',  MS-SSIM: x' behind a PSNR / SSIM line under --eval_msssim 1, nothing otherwise."""
+        return ",  MS-SSIM: %.4f" % acc['msssim'].avg if 'msssim' in acc else ""
+
     # ---- one iteration of each kind -------------------------------------------------------------
     def train_iteration(self, train_sample, epoch_idx, current_iter, do_evaluation=False):
         images, _ = train_sample
@@ -84,6 +89,9 @@ class ExperimentBuilder(object):
             psnr, ssim = utils.calc_metrics(output, target)
         metrics['psnr'].update(psnr)
         metrics['ssim'].update(float(ssim))
+        if getattr(self.args, 'eval_msssim', 0):      # the third metric, of the (stitched) frame; a NaN is reported as NaN
+            metrics['msssim'] = utils.AverageMeter()
+            metrics['msssim'].update(float(utils.msssim_rows(output.unsqueeze(0), target.unsqueeze(0))[0]))
         return losses, outputs, metrics
 
     def test_iteration(self, test_sample):
@@ -125,6 +133,8 @@ class ExperimentBuilder(object):
     # ---- sweeps ------------------------------------------------------------------------------
     def _validation_sweep(self, write_images=False):
         acc = {'psnr': utils.AverageMeter(), 'ssim': utils.AverageMeter()}
+        if getattr(self.args, 'eval_msssim', 0):
+            acc['msssim'] = utils.AverageMeter()
         val_losses = {}
         n = self.data.dataset.data_length['val']
         total = int(n / self.args.val_batch_size + 0.99)
@@ -154,7 +164,7 @@ class ExperimentBuilder(object):
         if args.mode == 'val':
             losses, acc = self._validation_sweep(write_images=True)
             print("%d examples processed" % acc['psnr'].count)
-            print("PSNR: %.2f,  SSIM: %.4f\n" % (acc['psnr'].avg, acc['ssim'].avg))
+            print("PSNR: %.2f,  SSIM: %.4f%s\n" % (acc['psnr'].avg, acc['ssim'].avg, self._msssim_suffix(acc)))
             return losses, acc
 
         last = int(args.total_iter_per_epoch * args.max_epoch)
@@ -172,7 +182,7 @@ class ExperimentBuilder(object):
                                                       self.build_loss_summary_string(losses, metrics)), flush=True)
                 if self.state['current_iter'] % args.total_iter_per_epoch == 0:
                     val_losses, acc = self._validation_sweep()
-                    print("validation PSNR: %.2f,  SSIM: %.4f\n" % (acc['psnr'].avg, acc['ssim'].avg))
+                    print("validation PSNR: %.2f,  SSIM: %.4f%s\n" % (acc['psnr'].avg, acc['ssim'].avg, self._msssim_suffix(acc)))
                     self.epoch += 1
                     psnr = acc['psnr'].avg
                     is_best = psnr > self.best_PSNR

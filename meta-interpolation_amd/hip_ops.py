@@ -845,6 +845,143 @@ def psnr_ssim(pred01, tgt01, want_sq_sum=False):
     return (res[:, 0], res[:, 1]) + ((sq,) if want_sq_sum else ())
 
 
+# --------------------------------------------------------------------------------------------
+# Multi-scale SSIM                      (pytorch_msssim/__init__.py:78-142; no branch of the reference's Loss uses it)
+# --------------------------------------------------------------------------------------------
+_MSSSIM_LEVELS = 5
+_MSSSIM_VAL_RANGES = {1: 0, 2: 1, 255: 2, 256: 3}
+
+
+def _msssim_dims(img1, fold):
+    """The call's (rows, C, H, W); fold: one value over the batch under a FIXED class -- the samples are further channel planes of one row."""
+    N, C, H, W = img1.shape
+    return (1, N * C, H, W) if fold else (N, C, H, W)
+
+
+def _msssim_launch(img1, img2, mode, normalize, quantize=False, fold=False):
+    """-> (result [rows], scratch): the forward launches of savfi_msssim_f32; `scratch` is what the backward needs."""
+    N, C, H, W = _msssim_dims(img1, fold)
+    res = torch.empty(1 if mode == _hip.SSIM_RANGE_BATCH else N, dtype=torch.float32, device=img1.device)
+    scratch = torch.empty(_workspace_floats("savfi_msssim_scratch_bytes", N, C, H, W) // 4, dtype=torch.float32, device=img1.device)
+    lib = _hip.lib()
+    _hip.launch("msssim", lambda: _hip.check(lib.savfi_msssim_f32(
+        img1.data_ptr(), img2.data_ptr(), res.data_ptr(), scratch.data_ptr(), N, C, H, W, mode, int(bool(normalize)), int(bool(quantize)),
+        _hip.current_stream()), "savfi_msssim_f32"), nbytes=int(8 * img1.numel() * 1.6))
+    return res, scratch
+
+
+class _MsSsim(torch.autograd.Function):
+    """img1, img2 [N,C,H,W] -> float32[N] (every sample an N = 1 call of the reference) or float32[1] (one call on the batch); the range
+    classes and the factors of the backward stay on the device (capturable); deterministic."""
+
+    @staticmethod
+    def forward(ctx, img1, img2, mode, normalize, fold):
+        _hip.require_cuda(img1, img2)
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("msssim differentiates w.r.t. the first image (the prediction) only")
+        res, scratch = _msssim_launch(img1, img2, mode, normalize, fold=fold)
+        ctx.mode, ctx.fold = mode, fold
+        ctx.scratch = scratch      # holds the backward's work area too: not a saved tensor (the backward writes into it)
+        ctx.save_for_backward(img1, img2)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        img1, img2 = ctx.saved_tensors
+        N, C, H, W = _msssim_dims(img1, ctx.fold)
+        g = g.contiguous()
+        g1 = torch.empty_like(img1)
+        scratch = ctx.scratch
+        lib = _hip.lib()
+        _hip.launch("msssim_bwd", lambda: _hip.check(lib.savfi_msssim_bwd_f32(
+            img1.data_ptr(), img2.data_ptr(), g.data_ptr(), scratch.data_ptr(), g1.data_ptr(), N, C, H, W, ctx.mode,
+            _hip.current_stream()), "savfi_msssim_bwd_f32"), nbytes=int(12 * img1.numel() * 1.6))
+        return g1, None, None, None, None
+
+
+@functools.lru_cache(maxsize=None)
+def _msssim_taps(n, device):
+    """The n fp32 taps of pytorch_msssim.gaussian(n, 1.5) on `device`."""
+    import math
+    g = torch.tensor([math.exp(-(x - n // 2) ** 2 / 4.5) for x in range(n)], dtype=torch.float32)
+    return (g / g.sum()).to(device)
+
+
+def _msssim_composed(img1, img2, per_sample, fixed_cls, normalize):
+    """The same value from differentiable device ops (what --second_order takes): separable windows, the range of every level decided
+    by torch.where on device tensors (no host read), avg_pool2d between the levels."""
+    C = img1.shape[1]
+    dims = (1, 2, 3) if per_sample else (0, 1, 2, 3)
+    ms, mc = [], []
+    for _ in range(_MSSSIM_LEVELS):
+        n = min(11, img1.shape[2], img1.shape[3])
+        taps = _msssim_taps(n, img1.device)
+        wr, wc = taps.view(1, 1, 1, n).expand(C, 1, 1, n), taps.view(1, 1, n, 1).expand(C, 1, n, 1)
+
+        def win(x):
+            return torch.nn.functional.conv2d(torch.nn.functional.conv2d(x, wr, groups=C), wc, groups=C)
+        if fixed_cls is None:
+            d = img1.detach()
+            hi, lo = d.amax(dims, keepdim=True), d.amin(dims, keepdim=True)
+            one = torch.ones_like(hi)
+            L = torch.where(hi > 128, 255 * one, one) + torch.where(lo < -0.5, one, 0 * one)
+        else:
+            L = (1.0, 2.0, 255.0, 256.0)[fixed_cls]
+        C1, C2 = (0.01 * L) ** 2, (0.03 * L) ** 2
+        mu1, mu2 = win(img1), win(img2)
+        s1, s2, s12 = win(img1 * img1) - mu1 * mu1, win(img2 * img2) - mu2 * mu2, win(img1 * img2) - mu1 * mu2
+        v1, v2 = 2 * s12 + C2, s1 + s2 + C2
+        smap = ((2 * mu1 * mu2 + C1) * v1) / ((mu1 * mu1 + mu2 * mu2 + C1) * v2)
+        ms.append(smap.mean(dims))
+        mc.append((v1 / v2).mean(dims))
+        img1, img2 = torch.nn.functional.avg_pool2d(img1, (2, 2)), torch.nn.functional.avg_pool2d(img2, (2, 2))
+    w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+    last = (ms[-1] + 1) / 2 if normalize else ms[-1]
+    out = last ** (4 * w[-1])
+    for s in range(_MSSSIM_LEVELS - 1):
+        out = out * ((mc[s] + 1) / 2 if normalize else mc[s]) ** w[s]
+    return out
+
+
+def _msssim_args(img1, img2, val_range, what="msssim"):
+    if img1.dim() != 4 or img1.shape != img2.shape or img1.shape[2] < 32 or img1.shape[3] < 32:
+        raise ValueError("%s needs two [N,C,H,W] tensors of one shape with H, W >= 32 (five levels, and the reference pools once more "
+                         "after the fifth), got %s, %s" % (what, tuple(img1.shape), tuple(img2.shape)))
+    if val_range is not None and val_range not in _MSSSIM_VAL_RANGES:
+        raise ValueError("%s: val_range must be None (decided from the data on every level) or one of 1, 2, 255, 256, got %r"
+                         % (what, val_range))
+    img1, img2 = img1.contiguous(), img2.contiguous()
+    _hip.require_cuda(img1, img2)
+    return img1, img2, None if val_range is None else _MSSSIM_VAL_RANGES[val_range]
+
+
+def msssim(img1, img2, val_range=None, normalize=False):
+    """pytorch_msssim.msssim(img1, img2, size_average=True, val_range=..., normalize=...) as implemented: one value over the whole
+    batch, ssim_4 ** (4 w_4) * prod cs_s ** w_s, NaN for a negative base.  Gradient for `img1` only."""
+    img1, img2, cls = _msssim_args(img1, img2, val_range)
+    if double_backward():
+        return _msssim_composed(img1, img2, False, cls, normalize).reshape(())
+    if cls is not None:
+        return _MsSsim.apply(img1, img2, _hip.SSIM_RANGE_FIXED + cls, normalize, True).reshape(())
+    return _MsSsim.apply(img1, img2, _hip.SSIM_RANGE_BATCH, normalize, False).reshape(())
+
+
+def msssim_per_sample(img1, img2, val_range=None, normalize=False):
+    """[N,C,H,W] x [N,C,H,W] -> [N]: msssim of every sample on its own (tasks adapted in lockstep)."""
+    img1, img2, cls = _msssim_args(img1, img2, val_range, "msssim_per_sample")
+    if double_backward():
+        return _msssim_composed(img1, img2, True, cls, normalize)
+    return _MsSsim.apply(img1, img2, _hip.SSIM_RANGE_PER_ROW if cls is None else _hip.SSIM_RANGE_FIXED + cls, normalize, False)
+
+
+def msssim_metric(pred01, tgt01):
+    """pred01, tgt01 [rows,C,H,W] in unit range -> [rows]: msssim(quantize(pred), quantize(target), val_range=255) of every row on its
+    own, the plain definition (NaN where a base is negative); the images are quantised as they are loaded.  No gradient; capturable."""
+    pred01, tgt01, _ = _msssim_args(pred01.detach(), tgt01.detach(), None, "msssim_metric")
+    return _msssim_launch(pred01, tgt01, _hip.SSIM_RANGE_FIXED + 2, False, quantize=True)[0]
+
+
 def frames_to_u8(x):
     """x [N,C,H,W] (or [C,H,W], [H,W]) in unit range, C = 1 or 3 -> uint8 [N,H,W,C] ([H,W,C], [H,W]) on the device, quantised as
     utils.save_image does (the metric's device function): a frame leaves the device as bytes."""

@@ -1,16 +1,32 @@
-"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM}.
+"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM, MSSSIM}.
 
 Surface follows the reference's ``Loss`` (loss.py:278-350): ``criterion(sr, hr) -> {TYPE: w*loss, ...,
 'total': sum}``.  L1 / MSE run on the fused savfi reduction kernel (one launch, no temporaries), SSIM on the fused
 window kernel of csrc/ssim.hip (forward and gradient, the reference's data-dependent dynamic range decided on the device);
 the reference's VGG / GAN / SuperSloMo terms are outside this path and are rejected loudly.
+
+MSSSIM is an ADDITION: the reference's ``Loss`` has no such branch, though the reference vendors ``pytorch_msssim.msssim``.  The term is
+``1 - msssim(sr, hr, normalize=True)`` with the data-dependent range of every level, on the multi-scale kernels of csrc/ssim.hip.
+``normalize=True`` because the plain product is NaN whenever a level's contrast mean is negative, which an untrained prediction gives.
 """
 import torch.nn as nn
 
 from . import hip_ops
 
-_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss}
-_KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample, 'SSIM': hip_ops.ssim_loss_per_sample}
+
+def msssim_loss(sr, hr):
+    """1 - msssim(sr, hr, normalize=True) as one value over the batch, the range of every level decided from `sr` (gradient for `sr` only)."""
+    return 1 - hip_ops.msssim(sr, hr, normalize=True)
+
+
+def msssim_loss_per_sample(sr, hr):
+    """[N]: the same term for every sample on its own, each an N = 1 call (tasks adapted in lockstep)."""
+    return 1 - hip_ops.msssim_per_sample(sr, hr, normalize=True)
+
+
+_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss, 'MSSSIM': msssim_loss}
+_KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample, 'SSIM': hip_ops.ssim_loss_per_sample,
+                       'MSSSIM': msssim_loss_per_sample}
 
 
 class Loss(nn.modules.loss._Loss):

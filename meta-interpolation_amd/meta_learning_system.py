@@ -455,6 +455,13 @@ class SceneAdaptiveInterpolation(nn.Module):
         images (reference utils.py:189-204 per pair): one call for all rows, no host read."""
         return utils.psnr_ssim_rows(self._to_unit_range(preds.detach()), self._to_unit_range(targets.detach()))
 
+    def _eval_msssim(self, preds, targets):
+        """--eval_msssim 1: the third metric of an evaluated frame, [rows] device values of msssim(quantize(pred), quantize(target),
+        val_range=255) (a NaN stays a NaN); None with the default."""
+        if not getattr(self.args, 'eval_msssim', 0):
+            return None
+        return utils.msssim_rows(self._to_unit_range(preds.detach()), self._to_unit_range(targets.detach()))
+
     def _task_body(self, frames, task_id, *, num_steps, use_second_order, msl, training_phase, do_evaluation, importance):
         """Everything one task contributes to a meta-iteration (reference :366-461): adaptation, target pass(es), its
         loss term, prediction, logging scalars.  Touches no shared mutable state, so tasks can run concurrently."""
@@ -477,6 +484,9 @@ class SceneAdaptiveInterpolation(nn.Module):
         if do_evaluation:
             mse, ssim = self._eval_metrics(target_preds, frames[self.target_idxs[1]][task_id:task_id + 1])
             res['mse'], res['ssim'] = mse[0], ssim[0]
+            msssim = self._eval_msssim(target_preds, frames[self.target_idxs[1]][task_id:task_id + 1])
+            if msssim is not None:
+                res['msssim'] = msssim[0]
         res['loss'] = torch.sum(torch.stack(task_losses))
         if not training_phase:
             self.net.restore_backup_stats()
@@ -621,18 +631,21 @@ class SceneAdaptiveInterpolation(nn.Module):
         preds = preds.detach()
         if do_evaluation:
             mse, ssim = self._eval_metrics(preds, frames[self.target_idxs[1]][list(ids)])
+            msssim = self._eval_msssim(preds, frames[self.target_idxs[1]][list(ids)])
         results = []
         for t in range(len(ids)):
             res = {'pred': self._to_unit_range(preds[t]).unsqueeze(0), 'logs': logs[t], 'loss': per_task[t]}
             if do_evaluation:
                 res['mse'], res['ssim'] = mse[t], ssim[t]
+                if msssim is not None:
+                    res['msssim'] = msssim[t]
             results.append(res)
         return results
 
     def _collect(self, num_tasks, local, results, importance, training_phase):
         """Fold the local tasks' results into what forward() returns, (losses, per-task predictions, metrics), and hand what is
         logged to _logging."""
-        total_losses, eval_mse, eval_ssim = [], [], []
+        total_losses, eval_mse, eval_ssim, eval_msssim = [], [], [], []
         deferred = _DeferredMeters()
         preds = [[] for _ in range(num_tasks)]
         for task_id, res in zip(local, results):
@@ -643,11 +656,15 @@ class SceneAdaptiveInterpolation(nn.Module):
             if 'mse' in res:
                 eval_mse.append(res['mse'])
                 eval_ssim.append(res['ssim'])
+                if 'msssim' in res:
+                    eval_msssim.append(res['msssim'])
         # mean over the GLOBAL meta-batch: local sum / B (the all-reduce of grads completes the mean)
         local_sum = torch.sum(torch.stack(total_losses)) if total_losses else torch.zeros((), device=self.device)
         losses = {'loss': local_sum / num_tasks}
         metrics = {'psnr': utils.AverageMeter(), 'ssim': utils.AverageMeter()}
-        self._logging(losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase)
+        if getattr(self.args, 'eval_msssim', 0):
+            metrics['msssim'] = utils.AverageMeter()
+        self._logging(losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase, eval_msssim)
         return losses, preds, metrics
 
     def _run_tasks(self, local, body, flatten=None, streams=None):
@@ -691,7 +708,7 @@ class SceneAdaptiveInterpolation(nn.Module):
             raise errors[0]
         for packed in results.values():                         # produced on a side stream, consumed on the caller's
             for res in ([packed] if flatten is None else flatten(packed)):
-                for v in [res['loss'], res['pred'], res.get('mse'), res.get('ssim')] + [v for _, v in res['logs']]:
+                for v in [res['loss'], res['pred'], res.get('mse'), res.get('ssim'), res.get('msssim')] + [v for _, v in res['logs']]:
                     if torch.is_tensor(v) and v.is_cuda:
                         v.record_stream(cur)
         return [results[t] for t in local]
@@ -770,20 +787,20 @@ class SceneAdaptiveInterpolation(nn.Module):
             return list(range(num_tasks))
         return self.task_parallel.local_tasks(num_tasks)
 
-    def _logging(self, losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase=True):
+    def _logging(self, losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase=True, eval_msssim=()):
         """Everything that is logged needs the device to have finished the forward passes.  During training that host sync
         is postponed until the outer backward and the optimizer step are queued (run_train_iter): waiting here would
         drain the queue and the backward would start with the host a whole launch queue behind the GPU."""
         if self._defer_logging:
             importance = importance.detach().clone()      # read later: not the live (learnable) vector an outer step may move
         finish = functools.partial(self._finish_logging, losses, metrics, deferred, eval_mse, eval_ssim, importance,
-                                   training_phase)
+                                   training_phase, eval_msssim)
         if self._defer_logging:
             self._pending_logging = finish
         else:
             finish()
 
-    def _finish_logging(self, losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase=True):
+    def _finish_logging(self, losses, metrics, deferred, eval_mse, eval_ssim, importance, training_phase=True, eval_msssim=()):
         """ONE host sync; fills `losses` and `metrics` in place."""
         meters = deferred.flush()
         if eval_mse:
@@ -792,6 +809,9 @@ class SceneAdaptiveInterpolation(nn.Module):
             for m, s in zip(mse, ssims):
                 metrics['psnr'].update(-10 * np.log10(m + 1e-8).item())
                 metrics['ssim'].update(s)
+        if eval_msssim:
+            for v in torch.stack(list(eval_msssim)).cpu().tolist():
+                metrics['msssim'].update(v)
         if self.task_parallel.active and training_phase:
             self._reduce_logging(losses, meters, metrics)
         for key, meter in meters.items():
@@ -888,7 +908,7 @@ class SceneAdaptiveInterpolation(nn.Module):
         vec = [float(losses['loss'].detach())]
         for k in keys:
             vec += [float(meters[k].sum), float(meters[k].count)]
-        for k in ('psnr', 'ssim'):
+        for k in [k for k in ('psnr', 'ssim', 'msssim') if k in metrics]:
             vec += [float(metrics[k].sum), float(metrics[k].count)]
         red = self.task_parallel.allreduce_scalars(torch.tensor(vec, dtype=torch.float64)).cpu().tolist()
         losses['loss_global'] = red[0]
@@ -897,7 +917,7 @@ class SceneAdaptiveInterpolation(nn.Module):
             meters[k].sum, meters[k].count = red[i], red[i + 1]
             meters[k].avg = red[i] / max(red[i + 1], 1)
             i += 2
-        for k in ('psnr', 'ssim'):
+        for k in [k for k in ('psnr', 'ssim', 'msssim') if k in metrics]:
             metrics[k].sum, metrics[k].count = red[i], red[i + 1]
             metrics[k].avg = red[i] / max(red[i + 1], 1)
             i += 2

@@ -90,6 +90,44 @@ def psnr_ssim_rows(pred01, tgt01):
             torch.stack([ssim(q_p[r:r + 1], q_t[r:r + 1], val_range=255) for r in rows]))
 
 
+def msssim_rows(pred01, tgt01):
+    """[rows,C,H,W] x [rows,C,H,W] in [0,1] -> [rows]: the metric of --eval_msssim 1, msssim(quantize(pred), quantize(target),
+    val_range=255) of every row on its own (pytorch_msssim/__init__.py:78-104 as implemented: NaN where a level's contrast mean is
+    negative).  Device tensors take the fused kernels (hip_ops.msssim_metric); host tensors the composition below, row by row.
+    H, W >= 32."""
+    pred01, tgt01 = pred01.detach(), tgt01.detach()
+    if pred01.is_cuda and tgt01.is_cuda:
+        from . import hip_ops
+        return hip_ops.msssim_metric(pred01, tgt01)
+    if min(pred01.shape[-2:]) < 32:
+        raise ValueError("msssim needs H, W >= 32, got %s" % (tuple(pred01.shape),))
+    q_p, q_t = quantize(pred01, 1.), quantize(tgt01, 1.)
+    w = torch.tensor([0.0448, 0.2856, 0.3001, 0.2363, 0.1333])
+    rows = []
+    for r in range(pred01.shape[0]):
+        a, b = q_p[r:r + 1], q_t[r:r + 1]
+        cs = []
+        for _ in range(5):
+            last, c = _ssim_and_cs(a, b, 255)
+            cs.append(c)
+            a, b = F.avg_pool2d(a, (2, 2)), F.avg_pool2d(b, (2, 2))
+        rows.append(torch.prod((torch.stack(cs) ** w)[:-1] * last ** w[-1]))
+    return torch.stack(rows)
+
+
+def _ssim_and_cs(img1, img2, val_range):
+    """(mean SSIM map, mean v1 / v2) of one level (pytorch_msssim/__init__.py:19-75 with full=True)."""
+    _, channel, height, width = img1.size()
+    win = _gauss_window(min(11, height, width), channel, img1.device)
+    conv = lambda t: F.conv2d(t, win, padding=0, groups=channel)
+    mu1, mu2 = conv(img1), conv(img2)
+    mu1_sq, mu2_sq, mu12 = mu1.pow(2), mu2.pow(2), mu1 * mu2
+    s1, s2, s12 = conv(img1 * img1) - mu1_sq, conv(img2 * img2) - mu2_sq, conv(img1 * img2) - mu12
+    C1, C2 = (0.01 * val_range) ** 2, (0.03 * val_range) ** 2
+    v1, v2 = 2.0 * s12 + C2, s1 + s2 + C2
+    return (((2 * mu12 + C1) * v1) / ((mu1_sq + mu2_sq + C1) * v2)).mean(), (v1 / v2).mean()
+
+
 # ---------------------------------------------------------------------------------------------
 # checkpoints: {'epoch', 'arch', 'state_dict', 'best_PSNR'} under checkpoint/<exp_name>/
 # ---------------------------------------------------------------------------------------------
