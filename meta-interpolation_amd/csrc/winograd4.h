@@ -21,15 +21,20 @@
 // layers), second pass along one transformed row, which leaves as 6 conflict-free ds_write_b32 into the other V buffer -- and that
 // patch row's registers are reloaded for the chunk after next (10-15 steps of 4 MFMAs ahead of their first use).  A fragments: 18
 // floats per lane and k-step from a pre-swizzled U (four 16-byte + one 8-byte load), reloaded in place half a chunk ahead; B
-// fragments: one ds_read_b64 per (point, k-step), two steps ahead.  Output stage: the 36 points of 16 channels meet in LDS
-// (bank-swizzled by the writer's row group), each thread finishes two (tile, channel) pairs per round: A^T M A (first pass packed),
-// bias / (leaky) ReLU (specialised per launch: 0-4 VALU per element), mask, row stores.
+// fragments: one ds_read_b64 per (point, k-step), two steps ahead.  Output stage, two rounds of 16 channels: the accumulator layout
+// holds the same (tile, channel) pairs in the same lane of all four waves, so wave w finishes tile w / 2 and the channel pair 2 (w % 2), + 1
+// of every lane -- its own 9 points stay in registers, the other 27 come lane to lane through LDS as 8-byte slots (27 writes + 27 reads
+// of 8 bytes per thread and round, lane-contiguous, no swizzle; the image of a round is the same 73.7 KB); each thread finishes two
+// (tile, channel) pairs per round: A^T M A (first pass packed over the two channels), bias / (leaky) ReLU (specialised per launch: 0-4
+// VALU per element), mask, row stores of 16 tiles x 4 channel planes per instruction.
 //
 // Measured (tools/r6/wino4_time.py, profiles/r06_wino4_*.txt; T = 4 x 2 samples unless N is given): 64 -> 64 @192x256 95 us = 307
 // direct-equivalent TFLOP/s (F(2x2): 170 us, split-bf16 direct: 142), 128 -> 128 @96x128 94 us = 309, 51 -> 51 @258x450 N = 32
 // 814 us = 211 (F(2x2): 1230), 32 -> 32 @384x512 164 us = 176 (HBM: 400 MB).  Timing-only ablations: the channel loop alone runs at
 // 0.75-0.8 of the fp32 matrix peak; what remains is every non-MFMA instruction (fp32 VALU shares the matrix pipe's datapath: the
 // transform's VALU does not hide under MFMAs), the output stage (14-26 %) and, for 51 channels, padding (56 x 64 of 51 x 51: 38 %).
+// With the lane-to-lane exchange (profiles/wino4_lane_exchange_*.txt, parent against this form on one box): 32 -> 32 @384x512 155 -> 151 us,
+// 51 -> 51 @258x450 N = 32 729 -> 715, 64 -> 64 @192x256 91 -> 90; LDS instructions of the kernel -21 %, bank conflicts 0.
 #pragma once
 
 namespace w4 {
@@ -39,7 +44,7 @@ constexpr int COB = 32;             // produced channels per workgroup
 constexpr int KC = 8;               // reduction channels per chunk
 constexpr int PTS = 36;
 constexpr int VBUF = PTS * KC * TT;           // floats per V buffer (36 KB)
-constexpr int XBUF = PTS * 16 * TT;           // exchange of one 16-channel round (72 KB)
+constexpr int XBUF = PTS * 16 * TT;           // exchange of one 16-channel round: [wave][q][pair][lane] 8-byte slots (72 KB)
 constexpr int LDS_FLOATS = XBUF > 2 * VBUF ? XBUF : 2 * VBUF;
 #ifndef SAVFI_W4_MAXC
 #define SAVFI_W4_MAXC 512
@@ -244,14 +249,14 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
   const size_t cplane = (size_t)a.H * a.W;
   const float* xp = a.x + (size_t)n * a.K * cplane;
 
-  // This thread's tile (row ty, column tx of the map's 4 x 4 tiles) is the same in the transform role (slot lane % 32) and in the output
-  // role (slot tid % 32).  ONE wave-uniform branch; everything else works from the per-lane tile.  A slot behind the list's last tile is
-  // not live: the roles put its rows below the map, so every load offset of it is the out-of-range 0x80000000 (it reads zeros) and its
-  // stores are dropped.
+  // The tile (row ty, column tx of the map's 4 x 4 tiles) of one of the workgroup's 32 slots: slot lane % 32 in the transform role, slots
+  // lane % 16 and lane % 16 + 16 in the output role.  ONE wave-uniform branch; everything else works from the per-lane tile.  A slot behind
+  // the list's last tile is not live: the roles put its rows below the map, so every load offset of it is the out-of-range 0x80000000 (it
+  // reads zeros) and its stores are dropped.
   const int tl = lane & 31;
-  auto tile_of = [&](int tbq, int& ty, int& tx) {
+  auto tile_of = [&](int tbq, int slot, int& ty, int& tx) {
     if (a.flat) {
-      const unsigned t = 32u * (unsigned)tbq + (unsigned)tl, tx4 = (unsigned)a.tx4;
+      const unsigned t = 32u * (unsigned)tbq + (unsigned)slot, tx4 = (unsigned)a.tx4;
       unsigned q = __umulhi(t, a.tx_mul);          // floor(t / tx4) or one less (t tx_mul / 2^32 > t / tx4 - 1)
       unsigned r = t - q * tx4;
       if (r >= tx4) { ++q; r -= tx4; }
@@ -261,15 +266,15 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
     }
     const int tsh = a.tile_shift, tbw = 1 << tsh, tbh = TT >> tsh;
     const int tby = tbq / a.tiles_x, tbx = tbq - tby * a.tiles_x;
-    ty = tby * tbh + (tl >> tsh);
-    tx = tbx * tbw + (tl & (tbw - 1));
+    ty = tby * tbh + (slot >> tsh);
+    tx = tbx * tbw + (slot & (tbw - 1));
     return true;
   };
 
   // ---- transform role: tile tl, channel kc of the chunk ----
   const int kc = 2 * w + (lane >> 5);
   int tyi, txi;
-  const bool live = tile_of(tb, tyi, txi);
+  const bool live = tile_of(tb, tl, tyi, txi);
   const int y0 = live ? 4 * tyi - a.off : a.H, x0 = live ? 4 * txi - a.off : 0;
   constexpr int WC = IN16 ? IN16 - 1 : 0;       // first column of a row's 16-byte load
   unsigned pv[6], pn[IN16 ? 6 : 1], pn2[IN16 == 2 ? 6 : 1];
@@ -495,135 +500,171 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
   __syncthreads();
 
   // ---- output stage ------------------------------------------------------------------------------------------------
-  // bias of this thread's output channels: round cb, pair qq -> channel i0 + 16 cb + (tid >> 5) + 8 qq (fetched here, behind the channel
-  // loop, where no store is outstanding yet: a load issued between stores waits for every older store's acknowledge)
+  // The accumulator layout puts the same (tile, channel) pairs into the same lane of all four waves: lane 16 kg + j holds tiles j + 16 t and
+  // channels 16 cb + 4 kg + r, only the points differ.  Per round wave w finishes, for every lane, the tile t = w / 2 and the channel pair
+  // r = 2 (w % 2), + 1 -- two NEIGHBOURING registers of one accumulator tile, so a pair is an 8-byte operand as it stands.  Its own 9 points
+  // never leave the registers; the other 27 come from the same lane of the other three waves: X[wave][q][pair 2 t + r / 2][lane], 8-byte
+  // slots, 27 ds_write_b64 and 27 ds_read_b64 per thread and round, lane-contiguous (no swizzle), where the channel-major exchange took
+  // 72 ds_write_b32 and 36 ds_read2st64_b32 and sent the quarter a thread could have kept through LDS as well.
+  // (the lane's indices are derived again behind the channel loop: what the stage computes from them must not be held through the loop)
+  int olane = lane;
+  asm volatile("" : "+v"(olane));
+  const int oj = olane & 15, okg = olane >> 4;
+  const int ot = w >> 1, oh = w & 1;               // this wave's tile half and channel pair
   const int split = a.nsplit > 1 ? 1 : 0;          // bias / activation / mask then happen in wino_split_reduce
   float* const obase = split ? a.partial + (size_t)sp * a.N * a.I * a.Ho * a.Wo : a.out;
+  // bias of this lane's channels of round cb, i0 + 16 cb + 4 kg + 2 oh + e (fetched here, behind the channel loop, where no store is
+  // outstanding yet: a load issued between stores waits for every older store's acknowledge)
   float bvals[2][2];
 #pragma unroll
   for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      const int i = i0 + 16 * cb + (tid >> 5) + 8 * qq;
-      bvals[cb][qq] = (a.bias && split == 0 && i < a.I) ? a.bias[task * a.I + i] : 0.f;
+    for (int e = 0; e < 2; ++e) {
+      const int i = i0 + 16 * cb + 4 * okg + 2 * oh + e;
+      bvals[cb][e] = (a.bias && split == 0 && i < a.I) ? a.bias[task * a.I + i] : 0.f;
     }
 
-  // this thread finishes pairs p = tid + 256 qq of a round: tile p % 32 (= tid % 32), channel p / 32 of the round's 16
-  const int otl = tid & 31, och = tid >> 5;
-  // (otl == tl.)  Decoded again, not held in two more registers through the channel loop -- except in the MASK instances, whose tightest
-  // spot is this stage (64 mask values): measured per instance on the compiler's spill counts, DESIGN.md 4i
-  int tbo = tb, oty = tyi, otx = txi;
-  bool olive = live;
-  if constexpr (!MASK) {
-    asm volatile("" : "+s"(tbo));
-    olive = tile_of(tbo, oty, otx);
-  }
-  const int oy = olive ? 4 * oty : a.Ho, ox = 4 * otx;    // a slot behind the last tile stores nothing
+  // this thread's tile, slot j + 16 ot, and the offsets of its rows: decoded here, not held in registers through the channel loop
+  int tbo = tb;
+  asm volatile("" : "+s"(tbo));
   const unsigned oplane = (unsigned)(a.Ho * a.Wo) * 4u;
   constexpr int NS = 4 / VECW;                     // stores per row
-  unsigned ooff[4][NS];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int e = 0; e < NS; ++e) {
-      const int x = ox + e * VECW;
-      const bool ok = oy + r < a.Ho && x < a.Wo;
-      if (a.out_unit16) ooff[r][e] = ok ? (unsigned)(((oy + r) * (a.Wo >> 4) + (x >> 4)) * a.I) * 64u + (unsigned)(x & 15) * 4u : 0x80000000u;
-      else ooff[r][e] = ok ? (unsigned)((oy + r) * a.Wo + x) * 4u + (unsigned)(lane >> 5) * oplane : 0x80000000u;
-    }
-  // planar: a descriptor over the wave's two channel planes of a pair (och = 2 w + lane / 32); a channel beyond I shrinks it
-  auto pair_rsrc = [&](const float* base, int cb, int qq, unsigned plane_bytes = 0) {
-    if (plane_bytes == 0) plane_bytes = oplane;
-    const int ie = i0 + 16 * cb + 2 * w + 8 * qq;        // the wave's even channel
-    const int have = a.I - ie < 0 ? 0 : (a.I - ie > 2 ? 2 : a.I - ie);
-    return w4_rsrc(base + ((size_t)n * a.I + (ie < a.I ? ie : 0)) * (plane_bytes >> 2), (unsigned)have * plane_bytes);
-  };
   // POOL: the tile's 2 x 2 pooled pixels, rows oy / 2 + {0, 1}, columns ox / 2 + {0, 1}; VECW 4: Wp is even, a row's two are one 8-byte
   // store (inside or outside the pooled map together); VECW 2: a dword each.  A pixel outside the floor-sized map is dropped.
   constexpr int PS = VECW == 4 ? 1 : 2;
   const unsigned pplane = POOL ? (unsigned)(a.Hp * a.Wp) * 4u : 0u;
+  // VECW 1: a row's first offset alone and the tile's columns inside the map (16 offsets, on top of the accumulators, spilled in the channel loop)
+  constexpr int NO = VECW == 1 ? 1 : NS;
+  unsigned ooff[4][NO];                            // planar: + the plane of the lane's even channel, 4 kg above the wave's first
+  int ocols;
+  auto ooff1 = [&](int r, int c) { return c < ocols ? ooff[r][0] + 4u * (unsigned)c : 0x80000000u; };
   unsigned poff[POOL ? 2 : 1][POOL ? PS : 1];
-  if constexpr (POOL) {
+  {
+    int oty, otx;
+    const bool olive = tile_of(tbo, oj + 16 * ot, oty, otx);
+    const int oy = olive ? 4 * oty : a.Ho, ox = 4 * otx;    // a slot behind the last tile stores nothing
+    ocols = a.Wo - ox;
 #pragma unroll
-    for (int r = 0; r < 2; ++r)
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int e = 0; e < PS; ++e) {
-        const int py = (oy >> 1) + r, px = (ox >> 1) + e;
-        poff[r][e] = (py < a.Hp && px < a.Wp) ? (unsigned)(py * a.Wp + px) * 4u + (unsigned)(lane >> 5) * pplane : 0x80000000u;
+      for (int e = 0; e < NO; ++e) {
+        const int x = ox + e * VECW;
+        const bool ok = oy + r < a.Ho && x < a.Wo;
+        if (a.out_unit16) ooff[r][e] = ok ? (unsigned)(((oy + r) * (a.Wo >> 4) + (x >> 4)) * a.I) * 64u + (unsigned)(x & 15) * 4u : 0x80000000u;
+        else ooff[r][e] = ok ? (unsigned)((oy + r) * a.Wo + x) * 4u + (unsigned)(4 * okg) * oplane : 0x80000000u;
       }
+    if constexpr (POOL) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int e = 0; e < PS; ++e) {
+          const int py = (oy >> 1) + r, px = (ox >> 1) + e;
+          poff[r][e] = (py < a.Hp && px < a.Wp) ? (unsigned)(py * a.Wp + px) * 4u + (unsigned)(4 * okg) * pplane : 0x80000000u;
+        }
+    }
   }
-  float mk[MASK ? 2 : 1][MASK ? 2 : 1][4][4];
-  if constexpr (MASK) {          // every mask value before the first store (one in-order counter for loads and stores)
+  // planar: one descriptor per (round, wave, e) that starts at channel i0 + 16 cb + 2 oh + e and ends with the tensor's last real channel:
+  // a lane whose channel, 4 kg planes above the first, does not exist falls out of range and is dropped (13 planes stay below the
+  // out-of-range offset 2^31 on every map a 32-bit offset addresses at all)
+  auto wave_rsrc = [&](const float* base, int cb, int e, unsigned plane_bytes) {
+    const int ie = i0 + 16 * cb + 2 * oh + e;        // the wave's first channel
+    const int have = a.I - ie < 0 ? 0 : (a.I - ie > 13 ? 13 : a.I - ie);
+    return w4_rsrc(base + ((size_t)n * a.I + (ie < a.I ? ie : 0)) * (plane_bytes >> 2), (unsigned)have * plane_bytes);
+  };
+  // MASK: a round's 32 mask values, requested before the round's first store (one in-order counter for loads and stores)
+  float mk[MASK ? 2 : 1][4][4];
+  auto fetch_mask = [&](int cb) {
+    if constexpr (MASK) {
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        const i32x4 mrs = w4_uniform(pair_rsrc(a.mask, cb, qq));
+      for (int ch = 0; ch < 2; ++ch) {
+        const i32x4 mrs = w4_uniform(wave_rsrc(a.mask, cb, ch, oplane));
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
           for (int e = 0; e < NS; ++e) {
             if constexpr (VECW == 4) {
               const f32x4 v = savfi_raw_buffer_load_x4(mrs, (int)ooff[r][e], 0, 0);
-              mk[cb][qq][r][0] = v.x; mk[cb][qq][r][1] = v.y; mk[cb][qq][r][2] = v.z; mk[cb][qq][r][3] = v.w;
+              mk[MASK ? ch : 0][r][0] = v.x; mk[MASK ? ch : 0][r][1] = v.y; mk[MASK ? ch : 0][r][2] = v.z; mk[MASK ? ch : 0][r][3] = v.w;
             } else if constexpr (VECW == 2) {
               const f32x2 v = savfi_raw_buffer_load_x2(mrs, (int)ooff[r][e], 0, 0);
-              mk[cb][qq][r][2 * e] = v.x; mk[cb][qq][r][2 * e + 1] = v.y;
+              mk[MASK ? ch : 0][r][2 * e] = v.x; mk[MASK ? ch : 0][r][2 * e + 1] = v.y;
             } else {
-              mk[cb][qq][r][e] = savfi_raw_buffer_load_x1(mrs, (int)ooff[r][e], 0, 0);
+              mk[MASK ? ch : 0][r][e] = savfi_raw_buffer_load_x1(mrs, (int)ooff1(r, e), 0, 0);
             }
           }
       }
-  }
+    }
+  };
+  // w is wave-uniform but no constant: the two steps that name accumulator registers by it run as one of four instantiations behind a
+  // scalar branch (indexed dynamically, the accumulators would live in scratch); the barriers stay outside the branch
+  auto by_wave = [&](auto&& f) {
+    switch (w) {
+      case 0: f(std::integral_constant<int, 0>{}); break;
+      case 1: f(std::integral_constant<int, 1>{}); break;
+      case 2: f(std::integral_constant<int, 2>{}); break;
+      default: f(std::integral_constant<int, 3>{}); break;
+    }
+  };
+  f32x2* const xl = reinterpret_cast<f32x2*>(lds) + olane;       // X[wave][q][pair][lane]: slot ((9 wave + q) 4 + pair) 64 + lane
   const float slope = a.slope;
+  // round cb: this wave's 27 foreign pairs into the image
+  auto put = [&](auto cb_tag) {
+    constexpr int cb = decltype(cb_tag)::value;
+    by_wave([&](auto wtag) {
+      constexpr int WV = decltype(wtag)::value;
 #pragma unroll
-  for (int cb = 0; cb < 2; ++cb) {
-    // X[xi][channel 0..15][tile ^ swizzle]: the four row groups of an accumulator tile (channels 4 kg + r) would meet in the same banks
+      for (int q = 0; q < 9; ++q)
 #pragma unroll
-    for (int q = 0; q < 9; ++q)
+        for (int p = 0; p < 4; ++p)
+          if (p != WV) xl[((9 * WV + q) * 4 + p) * 64] = (f32x2){acc[q][cb][p >> 1][2 * (p & 1)], acc[q][cb][p >> 1][2 * (p & 1) + 1]};
+    });
+  };
+  // A^T m over the rows of the 6 x 6 points, both channels of the pair at once (the 8-byte slots arrive as the packed operands)
+  auto gather = [&](auto cb_tag, f32x2 (&t4)[4][6]) {
+    constexpr int cb = decltype(cb_tag)::value;
+    by_wave([&](auto wtag) {
+      constexpr int WV = decltype(wtag)::value;
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int c = 0; c < 6; ++c) {
+        f32x2 m[6], o[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          lds[((9 * w + q) * 16 + 4 * kg + r) * 32 + ((16 * t + j) ^ (16 * (kg & 1)))] = acc[q][cb][t][r];
-    __syncthreads();
+        for (int r = 0; r < 6; ++r) {
+          const int xi = 6 * r + c, wp = xi / 9, q = xi % 9;
+          if (wp == WV) m[r] = (f32x2){acc[q][cb][WV >> 1][2 * (WV & 1)], acc[q][cb][WV >> 1][2 * (WV & 1) + 1]};
+          else m[r] = xl[((9 * wp + q) * 4 + WV) * 64];
+        }
+        at6p(m[0], m[1], m[2], m[3], m[4], m[5], o);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t4[r][c] = o[r];
+      }
+    });
+  };
+  auto store = [&](auto cb_tag, const f32x2 (&t4)[4][6]) {
+    constexpr int cb = decltype(cb_tag)::value;
     // ACT (wave-uniform, one branch per round): 0 = nothing to add (a data gradient), 1 = bias, 2 = bias + ReLU, 3 = bias + leaky ReLU --
     // 1 / 2 / 4 instead of 4 VALU per output element
     auto finish = [&](auto act_tag) {
       constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        const int chl = och + 8 * qq;
-        const int col = otl ^ (16 * ((chl >> 2) & 1));
-        f32x2 t4p[4][3];           // A^T m, two columns at a time (a ds_read2st64_b32 delivers the pair: 512 floats apart)
-#pragma unroll
-        for (int cp = 0; cp < 3; ++cp) {
-          f32x2 m[6], o[4];
-#pragma unroll
-          for (int r = 0; r < 6; ++r)
-            m[r] = (f32x2){lds[((6 * r + 2 * cp) * 16 + chl) * 32 + col], lds[((6 * r + 2 * cp + 1) * 16 + chl) * 32 + col]};
-          at6p(m[0], m[1], m[2], m[3], m[4], m[5], o);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) t4p[r][cp] = o[r];
-        }
-        const float b = bvals[cb][qq];
-        const int i = i0 + 16 * cb + chl;
-        const i32x4 ors = w4_uniform(a.out_unit16 ? w4_rsrc(obase + (size_t)n * a.I * a.Ho * a.Wo, (unsigned)a.I * oplane) : pair_rsrc(obase, cb, qq));
+      for (int ch = 0; ch < 2; ++ch) {
+        const float b = bvals[cb][ch];
+        const int i = i0 + 16 * cb + 4 * okg + 2 * oh + ch;
+        const i32x4 ors = w4_uniform(a.out_unit16 ? w4_rsrc(obase + (size_t)n * a.I * a.Ho * a.Wo, (unsigned)a.I * oplane) : wave_rsrc(obase, cb, ch, oplane));
         const unsigned choff = a.out_unit16 ? (i < a.I ? (unsigned)i * 64u : 0x40000000u) : 0u;      // (+ 0x80000000 of a dropped pixel: still out of range)
         i32x4 prs = ors;
-        if constexpr (POOL) prs = w4_uniform(pair_rsrc(a.pooled, cb, qq, pplane));
+        if constexpr (POOL) prs = w4_uniform(wave_rsrc(a.pooled, cb, ch, pplane));
         float ye[4];                 // POOL: the even row above, kept until its odd partner arrives
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float y[4];
-          at6(t4p[r][0].x, t4p[r][0].y, t4p[r][1].x, t4p[r][1].y, t4p[r][2].x, t4p[r][2].y, y);
+          at6(t4[r][0][ch], t4[r][1][ch], t4[r][2][ch], t4[r][3][ch], t4[r][4][ch], t4[r][5][ch], y);
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             float v = y[c];
             if constexpr (ACT >= 1) v += b;
             if constexpr (ACT == 2) v = fmaxf(v, 0.f);
             if constexpr (ACT == 3) v = fmaxf(v, 0.f) + slope * fminf(v, 0.f);
-            if constexpr (MASK) v = mk[MASK ? cb : 0][MASK ? qq : 0][r][c] > 0.f ? v : v * a.mask_slope;
+            if constexpr (MASK) v = mk[MASK ? ch : 0][r][c] > 0.f ? v : v * a.mask_slope;
             y[c] = v;
           }
           if constexpr (VECW == 4) {
@@ -633,7 +674,7 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
             savfi_raw_buffer_store_x2((f32x2){y[2], y[3]}, ors, (int)(ooff[r][1] + choff), 0, 0);
           } else {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) savfi_raw_buffer_store_x1(y[c], ors, (int)(ooff[r][c] + choff), 0, 0);
+            for (int c = 0; c < 4; ++c) savfi_raw_buffer_store_x1(y[c], ors, (int)(ooff1(r, c) + choff), 0, 0);
           }
           if constexpr (POOL) {
             if (r % 2 == 0) {
@@ -645,7 +686,7 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
                 savfi_raw_buffer_store_x2((f32x2){p0, p1}, prs, (int)poff[r >> 1][0], 0, 0);
               } else {
                 savfi_raw_buffer_store_x1(p0, prs, (int)poff[r >> 1][0], 0, 0);
-                savfi_raw_buffer_store_x1(p1, prs, (int)poff[r >> 1][1], 0, 0);
+                savfi_raw_buffer_store_x1(p1, prs, (int)poff[r >> 1][PS - 1], 0, 0);
               }
             }
           }
@@ -660,8 +701,22 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
     } else {
       finish(std::integral_constant<int, 3>{});
     }
-    __syncthreads();
-  }
+  };
+  // W0 | barrier | F0 | barrier | W1 | barrier | F1
+  using R0 = std::integral_constant<int, 0>;
+  using R1 = std::integral_constant<int, 1>;
+  f32x2 t4[4][6];
+  fetch_mask(0);
+  put(R0{});
+  __syncthreads();
+  gather(R0{}, t4);
+  store(R0{}, t4);
+  fetch_mask(1);
+  __syncthreads();              // every wave has read round 0's image
+  put(R1{});
+  __syncthreads();
+  gather(R1{}, t4);
+  store(R1{}, t4);
 }
 
 }  // namespace w4
