@@ -80,7 +80,8 @@ extern "C" {
  * savfi_bn_apply_relu_f32, savfi_bn_running_update_f32, savfi_maxpool2x2_f32, savfi_upnearest2x_add_f32, savfi_add_relu_f32,
  * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32; then savfi_conv3x3_f4_launched_workgroups, savfi_conv3x3_debug_f4_block_decode,
  * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32; then, for multi-scale
- * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32. */
+ * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32; then, for SepConv's second-order terms,
+ * savfi_sepconv_bwd2_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -108,6 +109,22 @@ int savfi_sepconv_fwd_f32(const float* in, const float* v, const float* h, float
 int savfi_sepconv_bwd_f32(const float* in, const float* v, const float* h, const float* gO,
                           float* gI, float* gV, float* gH,
                           int B, int C, int Ho, int Wo, int K, void* stream);
+
+/* The backward of the FILTER gradients above (second order; csrc/sepconv_bwd2.hip).  With gV, gH = the filter gradients of the op for the
+ * upstream gO, cotangents ggV of gV and ggH of gH (each [B,K,Ho,Wo]) and frames that carry no gradient, sep(.) the forward:
+ *   d_gO [B,C,Ho,Wo] = sep(in, ggV, h) + sep(in, v, ggH)
+ *   dV   [B,K,Ho,Wo] = the gV formula with h <- ggH         dH [B,K,Ho,Wo] = the gH formula with v <- ggV
+ * ggV or ggH may be NULL (= zero), not both.  Each of d_gO / dV / dH may be NULL (= not wanted), not all three.  dV needs ggH and dH
+ * needs ggV: asking for one whose cotangent is NULL is SAVFI_E_NULL (it would be all zero; the caller returns no gradient instead).
+ * fp32 operands and accumulators; every requested element is written exactly once from a sequential sum: no atomics, no pre-zeroing,
+ * no host read -- capturable and bit-reproducible.  One launch.  Any K, C; K = 51, C = 3 runs on the fp32 matrix cores.
+ * Errors, checked in this order before any launch: SAVFI_E_NULL (above); SAVFI_E_SHAPE (a dimension <= 0); SAVFI_E_UNSUPPORTED (an
+ * output pointer equal to an operand or to another output, or a pointer that is not 4-byte aligned); SAVFI_E_TOOBIG (the limits of
+ * savfi_sepconv_bwd_f32: B*K, B*C, Ho+K-1 <= 65535, Wo+K-1 < 2^31, tensors below 2^40 elements). */
+int savfi_sepconv_bwd2_f32(const float* in, const float* v, const float* h, const float* gO,
+                           const float* ggV, const float* ggH,
+                           float* d_gO, float* dV, float* dH,
+                           int B, int C, int Ho, int Wo, int K, void* stream);
 
 /* The same op on tap tensors that are slices of ONE interleaved buffer: sample b of v / h (and of gV / gH) starts tap_bstride planes of
  * Ho * Wo floats after sample b - 1 (tap_bstride = K: the contiguous layout of the two entry points above).  The package's SepConv plugin

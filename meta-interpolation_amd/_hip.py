@@ -39,6 +39,7 @@ _PROTOTYPES = {
     "savfi_version": [],
     "savfi_sepconv_fwd_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_sepconv_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "savfi_sepconv_bwd2_f32": [_P] * 9 + [c_int] * 5 + [_P],
     "savfi_sepconv_taps_strided_supported": [c_int] * 6,
     "savfi_sepconv_fwd_taps_strided_f32": [_P, _P, _P, _P] + [c_int] * 6 + [_P],
     "savfi_sepconv_bwd_taps_strided_f32": [_P, _P, _P, _P, _P, _P] + [c_int] * 6 + [_P],

@@ -18,6 +18,9 @@ Additions for the MI355X build (all optional, all default to the reference behav
                                (--graph_inner_loop) on fronts evaluated once per group; default 0: the sequential eager task loop
   --eval_msssim {0,1}          1: wherever PSNR / SSIM of an evaluated frame are computed, also its multi-scale SSIM, the metric `msssim` =
                                msssim(quantize(pred), quantize(target), val_range=255) (frames of 32 x 32 or more; NaN reported as NaN); default 0: dicts and summaries as before
+  --sepconv_second_order {0,1} --model sepconv --second_order: 1 carries the second-order terms through the 51-tap op (FunctionSepconvTwice, a fused
+                               second-backward kernel); default 0: the op's backward hands out graph-less gradients and they are dropped, as in the
+                               reference.  Has effect only in second-order passes
   --loss ...+w*MSSSIM          a term the reference's Loss has no branch for: 1 - msssim(sr, hr, normalize=True) on the fused multi-scale kernels
   --synthetic                  feed seeded synthetic septuplets instead of reading a dataset
 """
@@ -54,12 +57,12 @@ _FLAGS = {
     'MI355X': [
         ('fuse_support_pairs', int, 1), ('fuse_conv_act', int, 1), ('graph_inner_loop', int, -1), ('sepconv_window', int, 1),
         ('task_streams', int, -1), ('wgrad_overlap', int, 0), ('task_batch', int, 8), ('lazy_logging', int, 1),
-        ('dain_task_modes', int, 0), ('eval_msssim', int, 0),
+        ('dain_task_modes', int, 0), ('eval_msssim', int, 0), ('sepconv_second_order', int, 0),
         ('synthetic', 'flag', False),
     ],
 }
 
-_CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1]}
+_CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1], 'sepconv_second_order': [0, 1]}
 
 
 def build_parser():

@@ -17,8 +17,8 @@ from . import _hip
 
 # Set by the meta system for the duration of a forward with --second_order: ops whose hand-written backward
 # is not itself differentiable switch to composed device ops (losses) or refuse (voxel warp) instead of
-# silently dropping second-order terms.  (The sepconv op does drop them, exactly like the reference:
-# SURVEY.md section 0, fact 9.)
+# silently dropping second-order terms.  (FunctionSepconv does drop them, exactly like the reference: SURVEY.md
+# section 0, fact 9; --sepconv_second_order 1 makes the SepConv plugin use FunctionSepconvTwice in such passes.)
 # Per THREAD (tasks may be adapted on concurrent threads; two systems in one process must not flip each other's ops):
 # worker threads get the caller's value through meta_learning_system._run_tasks.
 _PASS = threading.local()

@@ -186,6 +186,9 @@ class SceneAdaptiveInterpolation(nn.Module):
             # --dain_task_modes 1: THIS MetaDAIN instance takes the lockstep and hipGraph paths (its class declines both)
             self.net.lockstep_tasks = True
             self.net.graph_capture = True
+        if hasattr(self.net, 'sepconv_second_order'):
+            # --sepconv_second_order 1: THIS SepConv plugin carries the second-order terms through its 51-tap op (second-order passes only)
+            self.net.sepconv_second_order = bool(int(getattr(args, 'sepconv_second_order', 0) or 0))
         if args.model == 'voxelflow':
             half = torch.full((3, 1, 1), 0.5 * 255, device=self.device)
             self.mean, self.std = half.clone(), half.clone()

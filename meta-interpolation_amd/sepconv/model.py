@@ -30,7 +30,7 @@ import torch.nn.functional as F
 from .. import hip_ops
 from ..hip_ops import Upsample2x, upsample_bilinear2x_window, upsample_window_sources
 from ..model_utils import MetaConv2dLayer, MetaSequential, as_view, fuse_conv_act, fuse_conv_chain, own_params_const, zero_grad_params
-from .sepconv_op.sepconv import FunctionSepconv, FunctionSepconvPair, frames8_supported
+from .sepconv_op.sepconv import FunctionSepconv, FunctionSepconvPair, FunctionSepconvTwice, frames8_supported
 
 TAPS_UNIT16 = True        # A/B (module attributes, no environment variable): False = planar taps / tap gradients
 GRADS_UNIT16 = True
@@ -78,6 +78,9 @@ class MetaNetwork(nn.Module):
         super().__init__()
         self.windowed = bool(windowed)
         self.batch_subnets = True     # windowed tail: the four Subnets as one launch per layer (A/B: set False on the instance)
+        # --sepconv_second_order 1 (set by the meta system on its instance): in second-order passes (hip_ops.double_backward()) the 51-tap
+        # op is FunctionSepconvTwice, whose backward carries a graph; False: FunctionSepconv, which drops those terms like the reference
+        self.sepconv_second_order = False
         self._windows = {}
         for i, (name, cin, cout) in enumerate(_ENCODER, start=1):
             setattr(self, name, _basic(cin, cout))
@@ -135,10 +138,11 @@ class MetaNetwork(nn.Module):
 
         if self.windowed and combine.is_cuda:
             return self._windowed_tail(tensorFirst, tensorSecond, combine, height, width, ph, pw, prep)
-        dot1 = FunctionSepconv.apply(self.modulePad(first).contiguous(),
-                                     self.moduleVertical1(combine), self.moduleHorizontal1(combine))
-        dot2 = FunctionSepconv.apply(self.modulePad(second).contiguous(),
-                                     self.moduleVertical2(combine), self.moduleHorizontal2(combine))
+        op = self._sepconv_op(combine)
+        dot1 = op.apply(self.modulePad(first).contiguous(),
+                        self.moduleVertical1(combine), self.moduleHorizontal1(combine))
+        dot2 = op.apply(self.modulePad(second).contiguous(),
+                        self.moduleVertical2(combine), self.moduleHorizontal2(combine))
         out = dot1 + dot2
         return out[:, :, HALF:HALF + height, HALF:HALF + width]
 
@@ -293,20 +297,32 @@ class MetaNetwork(nn.Module):
         r1 = prep['rim1'] if prep is not None and 'rim1' in prep else F.pad(frame1, rim, mode='replicate')
         return FunctionSepconvPair.apply(r0, r1, taps, unit16, grads16)
 
+    def _sepconv_op(self, x):
+        """The 51-tap op of this pass: the twice-differentiable one in second-order passes on a device with --sepconv_second_order 1.
+        Everything else between a fast weight and the loss is twice differentiable there already, or refuses: under
+        hip_ops.double_backward() no layer defers its activation derivative (MetaSequential.forward, _chain: no in_slope anywhere, no
+        pooled epilogue), the convolutions are ATen's (fuse_conv_act is off in such passes), and the pooling and the bilinear x2 are
+        linear Function pairs whose adjoints are Functions too."""
+        if self.sepconv_second_order and x.is_cuda and hip_ops.double_backward():
+            return FunctionSepconvTwice
+        return FunctionSepconv
+
     def _windowed_tail(self, frame0, frame1, combine, height, width, ph, pw, prep=None):
         win = self._window(height, width, ph, pw)
         cy0, cy1, cx0, cx1 = win['crop']
         crop = combine[:, :, cy0:cy1, cx0:cx1].contiguous()
-        if (self.batch_subnets and not frame0.requires_grad and not frame1.requires_grad
+        op = self._sepconv_op(combine)
+        # (the pair op and the task-batched Subnets are first order: the twice-differentiable op takes the Subnet-by-Subnet tail)
+        if (op is FunctionSepconv and self.batch_subnets and not frame0.requires_grad and not frame1.requires_grad
                 and FunctionSepconvPair.supported(frame0, crop.size(0), height, width, FILTER_TAPS)):
             return self._windowed_tail_batched(frame0, frame1, crop, win, prep)
         rim = (HALF,) * 4
-        dot1 = FunctionSepconv.apply(F.pad(frame0, rim, mode='replicate'),
-                                     self._subnet_window(self.moduleVertical1, crop, win),
-                                     self._subnet_window(self.moduleHorizontal1, crop, win))
-        dot2 = FunctionSepconv.apply(F.pad(frame1, rim, mode='replicate'),
-                                     self._subnet_window(self.moduleVertical2, crop, win),
-                                     self._subnet_window(self.moduleHorizontal2, crop, win))
+        dot1 = op.apply(F.pad(frame0, rim, mode='replicate'),
+                        self._subnet_window(self.moduleVertical1, crop, win),
+                        self._subnet_window(self.moduleHorizontal1, crop, win))
+        dot2 = op.apply(F.pad(frame1, rim, mode='replicate'),
+                        self._subnet_window(self.moduleVertical2, crop, win),
+                        self._subnet_window(self.moduleHorizontal2, crop, win))
         return dot1 + dot2
 
     def zero_grad(self, params=None):

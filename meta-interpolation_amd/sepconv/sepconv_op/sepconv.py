@@ -123,6 +123,129 @@ class FunctionSepconv(torch.autograd.Function):
         return gI, gV, gH
 
 
+class _SepconvFilterGrads(torch.autograd.Function):
+    """(input, vertical, horizontal, gradOutput[, cls]) -> (gradVertical, gradHorizontal): the backward of FunctionSepconvTwice as a
+    function of its own, through the entry points FunctionSepconv.backward uses.  Its backward is savfi_sepconv_bwd2_f32
+    (csrc/sepconv_bwd2.hip) and is once differentiable: a third derivative raises."""
+
+    @staticmethod
+    def forward(ctx, input, vertical, horizontal, gradOutput, cls, need_v, need_h):
+        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+        if not gradOutput.is_contiguous():
+            gradOutput = gradOutput.contiguous()
+        _hip.require_cuda(gradOutput)
+        gV = torch.empty_like(vertical) if need_v else None
+        gH = torch.empty_like(horizontal) if need_h else None
+        lib = _hip.lib()
+        if cls is not None and need_v and need_h:
+            _hip.launch("sepconv_bwd", lambda: _hip.check(lib.savfi_sepconv_bwd_frames8_f32(
+                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(), gV.data_ptr(), gH.data_ptr(),
+                cls.data_ptr(), B, C, Ho, Wo, K, K, 0, _hip.current_stream()), "savfi_sepconv_bwd_frames8_f32"),
+                nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
+        elif need_v or need_h:
+            p = lambda t: None if t is None else t.data_ptr()
+            _hip.launch("sepconv_bwd", lambda: _hip.check(lib.savfi_sepconv_bwd_f32(
+                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(),
+                None, p(gV), p(gH), B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_bwd_f32"),
+                nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=int(need_v) + int(need_h)))
+        ctx.save_for_backward(input, vertical, horizontal, gradOutput)
+        ctx.have = (need_v, need_h)
+        return gV, gH
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ggV, ggH):
+        input, vertical, horizontal, gradOutput = ctx.saved_tensors
+        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+        need_v, need_h, need_g = ctx.needs_input_grad[1:4]
+        # a gradient that was not computed has no cotangent; dV needs ggH and dH needs ggV (an absent one is zero: no gradient)
+        ggV = ggV.contiguous() if (ggV is not None and ctx.have[0]) else None
+        ggH = ggH.contiguous() if (ggH is not None and ctx.have[1]) else None
+        d_gO = torch.empty_like(gradOutput) if need_g and (ggV is not None or ggH is not None) else None
+        dV = torch.empty_like(vertical) if need_v and ggH is not None else None
+        dH = torch.empty_like(horizontal) if need_h and ggV is not None else None
+        if d_gO is not None or dV is not None or dH is not None:
+            _hip.require_cuda(*[t for t in (ggV, ggH) if t is not None])
+            lib = _hip.lib()
+            p = lambda t: None if t is None else t.data_ptr()
+            n_out = sum(t is not None for t in (dV, dH))
+            _hip.launch("sepconv_bwd2", lambda: _hip.check(lib.savfi_sepconv_bwd2_f32(
+                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(), p(ggV), p(ggH),
+                p(d_gO), p(dV), p(dH), B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_bwd2_f32"),
+                nbytes=bwd2_algorithmic_bytes(B, C, Ho, Wo, K, int(ggV is not None) + int(ggH is not None), d_gO is not None, n_out))
+        return None, dV, dH, d_gO, None, None, None
+
+
+def bwd2_algorithmic_bytes(B, C, Ho, Wo, K, cotangents=2, want_gO=True, tap_outputs=2):
+    """HBM bytes of savfi_sepconv_bwd2_f32 if every operand is read / written exactly once: input halo + v + h + gO + the cotangents
+    + d_gO + one [B,K,Ho,Wo] plane set per tap output."""
+    return 4 * (B * C * (Ho + K - 1) * (Wo + K - 1) + (2 + cotangents + tap_outputs) * B * K * Ho * Wo
+                + (1 + int(want_gO)) * B * C * Ho * Wo)
+
+
+def bwd2_macs(B, C, Ho, Wo, K, cotangents=2, want_dH=True):
+    """multiply-adds of the three window contractions (T, T' and D of csrc/sepconv_bwd2.hip): C K^2 per pixel each"""
+    n = (1 if cotangents == 2 else 0) + 1 + int(want_dH)
+    return n * B * C * Ho * Wo * K * K
+
+
+class FunctionSepconvTwice(torch.autograd.Function):
+    """FunctionSepconv for frames WITHOUT gradient, twice differentiable in the taps (--sepconv_second_order 1).
+
+        FunctionSepconvTwice.apply(input[B,C,Ho+K-1,Wo+K-1], vertical[B,K,Ho,Wo], horizontal[B,K,Ho,Wo]) -> output[B,C,Ho,Wo]
+
+    The forward and the first-order gradients go through the entry points of FunctionSepconv: same bits.  The backward is itself an
+    autograd.Function (_SepconvFilterGrads), so under create_graph=True the tap gradients carry a graph and the second-order terms
+    of MAML -- which FunctionSepconv, like the reference's op, drops silently -- reach the outer gradient through
+    savfi_sepconv_bwd2_f32.  A frame that requires grad is refused: the second-order terms of gI are not built, and an op that
+    returned a graph-less gI here would drop them silently.  FunctionSepconv remains the op to use for gI."""
+
+    @staticmethod
+    def forward(ctx, input, vertical, horizontal):
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("FunctionSepconvTwice: the frame requires grad, and the second-order terms of the input gradient "
+                                      "are not implemented (they would be dropped silently); use FunctionSepconv for gI")
+        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+        assert input.is_contiguous() and vertical.is_contiguous() and horizontal.is_contiguous()
+        if not input.is_cuda:
+            raise NotImplementedError("FunctionSepconvTwice has no CPU path (neither does the reference's op)")
+        _hip.require_cuda(input, vertical, horizontal)
+        output = torch.empty((B, C, Ho, Wo), dtype=input.dtype, device=input.device)
+        lib = _hip.lib()
+        cls = None
+        if frames8_supported(input, B, C, Ho, Wo, K):
+            cls = frames8_classify(input)
+            rc = [0]
+
+            def run8():
+                rc[0] = lib.savfi_sepconv_fwd_frames8_f32(input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
+                                                          cls.data_ptr(), B, C, Ho, Wo, K, K, 0, _hip.current_stream())
+                if rc[0] != _E_UNSUPPORTED:
+                    _hip.check(rc[0], "savfi_sepconv_fwd_frames8_f32")
+            _hip.launch("sepconv_fwd", run8, nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
+            if rc[0] == _E_UNSUPPORTED:
+                cls = None
+        if cls is None:
+            _hip.launch("sepconv_fwd", lambda: _hip.check(lib.savfi_sepconv_fwd_f32(
+                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
+                B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_fwd_f32"),
+                nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
+            ctx.save_for_backward(input, vertical, horizontal)
+        else:
+            ctx.save_for_backward(input, vertical, horizontal, cls)
+        return output
+
+    @staticmethod
+    def backward(ctx, gradOutput):
+        input, vertical, horizontal = ctx.saved_tensors[:3]
+        cls = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        _, need_v, need_h = ctx.needs_input_grad
+        if not (need_v or need_h):
+            return None, None, None
+        gV, gH = _SepconvFilterGrads.apply(input, vertical, horizontal, gradOutput, cls, need_v, need_h)
+        return None, gV, gH
+
+
 class FunctionSepconvPair(torch.autograd.Function):
     """sepconv(input0, taps[0::4], taps[1::4]) + sepconv(input1, taps[2::4], taps[3::4]) on an INTERLEAVED tap tensor.
 
