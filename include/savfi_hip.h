@@ -81,7 +81,7 @@ extern "C" {
  * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32; then savfi_conv3x3_f4_launched_workgroups, savfi_conv3x3_debug_f4_block_decode,
  * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32; then, for multi-scale
  * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32; then, for SepConv's second-order terms,
- * savfi_sepconv_bwd2_f32. */
+ * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -453,6 +453,12 @@ int savfi_upsample2x_window_bwd_f32(const float* gout, float* gin, int planes, i
 int savfi_upsample2x_window_bwd_masked_f32(const float* gout, const float* y, float slope, float* gin, int planes, int H, int W,
                                            int sy0, int sx0, int Hs, int Ws, int oy0, int ox0, int Hw, int Ww, int align_corners,
                                            void* stream);
+/* Which kernel the adjoint entries above run for `planes` crops of Hs x Ws source pixels (the launcher asks the same function):
+ *   0  one thread per source pixel (Ws < 32);   1  the LDS-tiled form;   8, 16, 32  the streaming form with strips of that many source
+ *   rows -- the first of 32, 16, 8 at which cdiv(Ws, 64) * cdiv(Hs, rows) * planes >= 8192, the tiled form if none.
+ * Host only: launches nothing, touches no device.  SAVFI_E_SHAPE for an argument <= 0.  tests/test_upsample_forms_gpu.py holds every
+ * form to float64 and the forms to each other. */
+int savfi_upsample2x_bwd_form(int planes, int Hs, int Ws);
 
 /* ----------------------------------------------------------------------------------
  * 3x3 / stride 1 / zero-pad 1 convolution of the backbones (sepconv/model.py:172-245 Basic / Subnet /

@@ -397,6 +397,23 @@ int check_window(const Win& g, int planes) {
   return 0;
 }
 
+// Which adjoint kernel a launch of `planes` crops of Hs x Ws source pixels runs (all arguments > 0): 0 = upsample2x_bwd (one thread per
+// source pixel), 1 = upsample2x_bwd_tiled, 8 / 16 / 32 = upsample2x_bwd_strip with that USR.  The ONE place where the form is decided:
+// the launcher and savfi_upsample2x_bwd_form both ask here.
+#ifndef SAVFI_UPSAMPLE_BWD_FORM
+#define SAVFI_UPSAMPLE_BWD_FORM 0      // variant builds: 1 = the tiled form of rounds 2-4, 2 = the streaming form at USR 32 wherever Ws allows it
+#endif
+int bwd_form(int planes, int Hs, int Ws) {
+  constexpr int form = SAVFI_UPSAMPLE_BWD_FORM;
+  if (Ws < 32) return 0;
+  // the streaming form where it has the waves to hide its serial walk (>= 8 per SIMD at some strip height), else the tiled form
+  int usr = 0;
+  for (int cand = 32; cand >= 8 && !usr; cand >>= 1)
+    if ((int64_t)savfi_cdiv(Ws, USW) * savfi_cdiv(Hs, cand) * planes >= 8192) usr = cand;
+  if (form == 2) usr = 32;
+  return (form != 1 && usr) ? usr : 1;
+}
+
 }  // namespace
 
 extern "C" int savfi_upsample2x_window_fwd_f32(const float* in, float* out, int planes, int H, int W, int sy0, int sx0,
@@ -423,19 +440,11 @@ extern "C" int savfi_upsample2x_window_bwd_masked_f32(const float* gout, const f
   const UpMask um{y, slope};
   const Win g{H, W, sy0, sx0, Hs, Ws, oy0, ox0, Hw, Ww, align_corners ? 1 : 0};
   if (int rc = check_window(g, planes)) return rc;
-#ifndef SAVFI_UPSAMPLE_BWD_FORM
-#define SAVFI_UPSAMPLE_BWD_FORM 0      // variant builds: 1 = the tiled form of rounds 2-4
-#endif
-  constexpr int form = SAVFI_UPSAMPLE_BWD_FORM;
-  // the streaming form where it has the waves to hide its serial walk (>= 8 per SIMD at some strip height), else the tiled form
-  int usr = 0;
-  for (int cand = 32; cand >= 8 && !usr; cand >>= 1)
-    if ((int64_t)savfi_cdiv(Ws, USW) * savfi_cdiv(Hs, cand) * planes >= 8192) usr = cand;
-  if (form == 2) usr = 32;
-  if (Ws >= 32 && form != 1 && usr) {
-    dim3 grid(savfi_cdiv(savfi_cdiv(Ws, USW) * savfi_cdiv(Hs, usr), 4), planes, 1);
-    hipLaunchKernelGGL(upsample2x_bwd_strip, grid, dim3(256), 0, (hipStream_t)stream, gout, gin, g, usr, um);
-  } else if (Ws >= 32) {      // the separable, LDS-tiled form
+  const int form = bwd_form(planes, Hs, Ws);
+  if (form >= 8) {            // the streaming form, USR = form
+    dim3 grid(savfi_cdiv(savfi_cdiv(Ws, USW) * savfi_cdiv(Hs, form), 4), planes, 1);
+    hipLaunchKernelGGL(upsample2x_bwd_strip, grid, dim3(256), 0, (hipStream_t)stream, gout, gin, g, form, um);
+  } else if (form == 1) {     // the separable, LDS-tiled form
     dim3 grid(savfi_cdiv(Hs, UBH) * savfi_cdiv(Ws, UBW), planes, 1);
     hipLaunchKernelGGL(upsample2x_bwd_tiled, grid, dim3(256), 0, (hipStream_t)stream, gout, gin, g, um);
   } else {
@@ -453,4 +462,9 @@ extern "C" int savfi_upsample2x_fwd_f32(const float* in, float* out, int planes,
 extern "C" int savfi_upsample2x_bwd_f32(const float* gout, float* gin, int planes, int H, int W, int align_corners,
                                         void* stream) {
   return savfi_upsample2x_window_bwd_f32(gout, gin, planes, H, W, 0, 0, H, W, 0, 0, 2 * H, 2 * W, align_corners, stream);
+}
+
+extern "C" int savfi_upsample2x_bwd_form(int planes, int Hs, int Ws) {
+  if (planes <= 0 || Hs <= 0 || Ws <= 0) return SAVFI_E_SHAPE;
+  return bwd_form(planes, Hs, Ws);
 }

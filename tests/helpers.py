@@ -60,6 +60,35 @@ def assert_fp_close(got, want, rtol=1e-5, what="", extra_abs=0.0):
     assert abs(got[1] - want[1]) <= rtol * scale + FP_ATOL + extra_abs, (what, got[1], want[1])
 
 
+CANARY = 7777.0
+PAD = 64                  # floats of canary on either side of a buffer the kernels write (256 bytes: the payload stays aligned)
+
+
+class Guarded:
+    """Device outputs inside canary-padded buffers: new(name, *shape) hands out a view, check() asserts nothing around any of them
+    changed."""
+
+    def __init__(self, device="cuda"):
+        self.bufs, self.device = {}, device
+
+    def new(self, name, *shape, fill=None):
+        n = int(np.prod(shape))
+        buf = torch.full((n + 2 * PAD,), CANARY, device=self.device)
+        view = buf[PAD:PAD + n]
+        if fill is not None:
+            view.fill_(fill)
+        self.bufs[name] = (buf, n)
+        return view.view(*shape)
+
+    def check(self, where):
+        for name, (buf, n) in self.bufs.items():
+            assert bool((buf[:PAD] == CANARY).all()) and bool((buf[PAD + n:] == CANARY).all()), "%s: wrote outside %s" % (where, name)
+
+    def untouched(self, name):
+        buf, n = self.bufs[name]
+        return bool((buf == CANARY).all())
+
+
 def build_system(model, overrides, fuse=1, device="cuda"):
     """Product system with seeded weights.  Execution-mode switches are pinned to the plain eager loop unless a test asks for a
     mode (`graph_inner_loop`, `task_batch`, `task_streams` in `overrides`): the fixture tests hook update_params per step."""

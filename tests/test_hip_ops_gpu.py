@@ -1408,10 +1408,17 @@ def test_all_taps_weight_gradient_matches_float64_and_hands_out_the_bias_gradien
 
 
 @pytest.mark.parametrize("shape,geom_kind,slope", [((3, 5, 12, 16), "full", 0.0), ((2, 64, 40, 70), "full", 0.2), ((2, 7, 31, 45), "window", 0.0),
-                                                   ((1, 3, 100, 130), "window", 0.0), ((4, 33, 9, 8), "full", 0.0)])
+                                                   ((1, 3, 100, 130), "window", 0.0), ((4, 33, 9, 8), "full", 0.0),
+                                                   ((1, 2048, 41, 70), "full", 0.2), ((1, 1400, 41, 70), "window", 0.0),
+                                                   ((1, 700, 41, 70), "window", 0.2)])
 def test_upsample_adjoint_folds_the_producers_relu_derivative(shape, geom_kind, slope):
     """savfi_upsample2x_window_bwd_masked_f32 (all three kernel forms: small maps, the tiled and the streaming one): the adjoint of the
-    bilinear x2 times (y > 0 ? 1 : slope) of its own input == the plain adjoint followed by savfi_bias_act_bwd_f32's derivative, bit for bit."""
+    bilinear x2 times (y > 0 ? 1 : slope) of its own input == the plain adjoint followed by savfi_bias_act_bwd_f32's derivative, bit for bit.
+    The form each case runs is the library's own answer (savfi_upsample2x_bwd_form: 0 per pixel, 1 tiled, 8 / 16 / 32 streaming with strips
+    of that many rows); the plain adjoint of every form is held to float64 in tests/test_upsample_forms_gpu.py."""
+    want_form = {(3, 5, 12, 16): 0, (2, 64, 40, 70): 1, (2, 7, 31, 45): 1, (1, 3, 100, 130): 1, (4, 33, 9, 8): 0,
+                 (1, 2048, 41, 70): 32, (1, 1400, 41, 70): 16, (1, 700, 41, 70): 8}[shape]
+    assert _hip.lib().savfi_upsample2x_bwd_form(shape[0] * shape[1], shape[2], shape[3]) == want_form
     g = torch.Generator().manual_seed(shape[2] * 7 + shape[3])
     x = torch.randn(*shape, generator=g).to(DEV)
     if geom_kind == "full":

@@ -10,42 +10,16 @@ import torch
 
 from meta_interpolation_amd import _hip, hip_ops
 from tests import small_ops_ref as R
+from tests.helpers import CANARY, PAD, Guarded as _Guarded       # canary-padded device buffers (shared with test_upsample_forms_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-CANARY = 7777.0
-PAD = 64                  # floats of canary on either side of a buffer the kernels write (256 bytes: the payload stays aligned)
 E_SHAPE, E_UNSUPPORTED = -2, -3
 
 
 def _rel(a, b):
     return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-12)
-
-
-class _Guarded:
-    """Device outputs inside canary-padded buffers: new(name, *shape) hands out a view, check() asserts nothing around any of them
-    changed."""
-
-    def __init__(self):
-        self.bufs = {}
-
-    def new(self, name, *shape, fill=None):
-        n = int(np.prod(shape))
-        buf = torch.full((n + 2 * PAD,), CANARY, device=DEV)
-        view = buf[PAD:PAD + n]
-        if fill is not None:
-            view.fill_(fill)
-        self.bufs[name] = (buf, n)
-        return view.view(*shape)
-
-    def check(self, where):
-        for name, (buf, n) in self.bufs.items():
-            assert bool((buf[:PAD] == CANARY).all()) and bool((buf[PAD + n:] == CANARY).all()), "%s: wrote outside %s" % (where, name)
-
-    def untouched(self, name):
-        buf, n = self.bufs[name]
-        return bool((buf == CANARY).all())
 
 
 # =============================================================================================
