@@ -81,7 +81,8 @@ extern "C" {
  * savfi_charbonnier_f32, savfi_charbonnier_bwd_f32; then savfi_conv3x3_f4_launched_workgroups, savfi_conv3x3_debug_f4_block_decode,
  * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32; then, for multi-scale
  * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32; then, for SepConv's second-order terms,
- * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form. */
+ * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form; then, for the Laplacian-pyramid loss term, savfi_laploss_scratch_bytes,
+ * savfi_laploss_f32, savfi_laploss_bwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -413,6 +414,33 @@ int savfi_msssim_f32(const float* img1, const float* img2, float* result, void* 
                      int range_mode, int normalize, int quantize, void* stream);
 int savfi_msssim_bwd_f32(const float* img1, const float* img2, const float* g_out, void* scratch, float* g_img1, int rows,
                          int C, int H, int W, int range_mode, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Laplacian-pyramid L1 loss term `Lap` and its gradient (csrc/laploss.hip), added under ABI 24.  `rows` independent losses per call.
+ *   sr, hr [rows, C, H, W] (prediction, target); levels = L in 2..5 (SAVFI_E_UNSUPPORTED otherwise).
+ *   g = [1, 4, 6, 4, 1] / 16, window g g^T per plane, borders by reflection about the border samples (pad 2).  c_0 = sr - hr and, for
+ *   s = 0 .. L - 2 on H_s x W_s planes (H_0 = H, H_{s+1} = ceil(H_s / 2), W alike):
+ *     c_{s+1} = (G c_s)[::2, ::2]        b_s = c_s - 4 G z_s,  z_s = zeros with c_{s+1} at the even positions, H_s x W_s
+ *   and b_{L-1} = c_{L-1}.  result[r] = sum_s 2^s sum |b_s| / (C H W), sums over the planes of row r; fully overwritten.
+ *   Every filtered level (s <= L - 2) needs H_s, W_s >= 3, SAVFI_E_SHAPE otherwise (L = 5: H, W >= 17; with `levels` out of range the
+ *   shape is judged for the nearest legal value, so that SHAPE precedes UNSUPPORTED); rows * C <= 65535 and H * W < 2^31,
+ *   SAVFI_E_TOOBIG otherwise.  One value over a batch: call with rows = 1 and C = N * C (the samples are further planes).
+ *   One launch per filtered level and a finish.  Band elements are fp32; their sums are carried in double.  No atomics, no cleared
+ *   memory, no host read: capturable and bit-reproducible.  Operands need 4-byte alignment only.
+ *   `scratch`: savfi_laploss_scratch_bytes(rows, C, H, W, levels) bytes, 16-byte aligned, caller-owned.  In 32-bit words, every
+ *   region rounded up to a multiple of four, P = rows * C:
+ *     c_s, s = 1 .. L - 1:              P H_s W_s floats each
+ *     g_{c_s}, s = 1 .. L - 2:          P H_s W_s floats each (written by the backward)
+ *     partial sums, s = 0 .. L - 2:     one double (two words) per workgroup, P ceil(H_s / 32) ceil(W_s / 32) of them
+ *   bwd: call with the forward's arguments and its scratch untouched.  g_sr [rows, C, H, W] = g_loss[r] * d result[r] / d sr, every
+ *   element written once, coarse to fine with one launch per filtered level; sign(b_s) is recomputed from the c_s the forward left,
+ *   by the forward's own device functions, and sign(0) = 0: an identical pair gives value 0 and gradient 0 exactly.  hr gets no gradient.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_laploss_scratch_bytes(int rows, int C, int H, int W, int levels);
+int savfi_laploss_f32(const float* sr, const float* hr, float* result, void* scratch, int rows, int C, int H, int W, int levels,
+                      void* stream);
+int savfi_laploss_bwd_f32(const float* sr, const float* hr, const float* g_loss, void* scratch, float* g_sr, int rows, int C, int H,
+                          int W, int levels, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:

@@ -22,6 +22,8 @@ Additions for the MI355X build (all optional, all default to the reference behav
                                second-backward kernel); default 0: the op's backward hands out graph-less gradients and they are dropped, as in the
                                reference.  Has effect only in second-order passes
   --loss ...+w*MSSSIM          a term the reference's Loss has no branch for: 1 - msssim(sr, hr, normalize=True) on the fused multi-scale kernels
+  --loss ...+w*Lap             another one: the Laplacian-pyramid L1 (five levels, 5-tap binomial window, reflected borders, low-pass residual last,
+                               sum_s 2^s sum |b_s| / n_0) on the fused kernels of csrc/laploss.hip; frames of 17 x 17 or more
   --synthetic                  feed seeded synthetic septuplets instead of reading a dataset
 """
 import argparse

@@ -982,6 +982,112 @@ def msssim_metric(pred01, tgt01):
     return _msssim_launch(pred01, tgt01, _hip.SSIM_RANGE_FIXED + 2, False, quantize=True)[0]
 
 
+# --------------------------------------------------------------------------------------------
+# Laplacian-pyramid L1, the term 'Lap' of --loss          (no counterpart in the reference; definition: include/savfi_hip.h)
+# --------------------------------------------------------------------------------------------
+LAP_LEVELS = 5
+
+
+def _lap_dims(sr, fold):
+    """The call's (rows, C, H, W); fold: one value over the batch -- the samples are further channel planes of one row."""
+    N, C, H, W = sr.shape
+    return (1, N * C, H, W) if fold else (N, C, H, W)
+
+
+class _LapLoss(torch.autograd.Function):
+    """sr, hr [N,C,H,W] -> float32[N] (every sample on its own) or float32[1] (fold: one value over the batch); capturable; deterministic."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, levels, fold):
+        _hip.require_cuda(sr, hr)
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("lap_loss differentiates w.r.t. the prediction only")
+        rows, C, H, W = _lap_dims(sr, fold)
+        res = torch.empty(rows, dtype=torch.float32, device=sr.device)
+        scratch = torch.empty(_workspace_floats("savfi_laploss_scratch_bytes", rows, C, H, W, levels) // 4, dtype=torch.float32,
+                              device=sr.device)
+        lib = _hip.lib()
+        _hip.launch("laploss", lambda: _hip.check(lib.savfi_laploss_f32(
+            sr.data_ptr(), hr.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, C, H, W, levels, _hip.current_stream()),
+            "savfi_laploss_f32"), nbytes=int(4 * sr.numel() * (2 + 2 / 3)))
+        ctx.levels, ctx.fold = levels, fold
+        ctx.scratch = scratch      # the pyramid of the difference, and the backward's work area: not a saved tensor (the backward writes into it)
+        ctx.save_for_backward(sr, hr)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        sr, hr = ctx.saved_tensors
+        rows, C, H, W = _lap_dims(sr, ctx.fold)
+        g = g.contiguous()
+        gsr = torch.empty_like(sr)
+        scratch = ctx.scratch
+        lib = _hip.lib()
+        _hip.launch("laploss_bwd", lambda: _hip.check(lib.savfi_laploss_bwd_f32(
+            sr.data_ptr(), hr.data_ptr(), g.data_ptr(), scratch.data_ptr(), gsr.data_ptr(), rows, C, H, W, ctx.levels,
+            _hip.current_stream()), "savfi_laploss_bwd_f32"), nbytes=int(4 * sr.numel() * (4 + 1 / 3)))
+        return gsr, None, None, None
+
+
+@functools.lru_cache(maxsize=None)
+def _lap_window(device):
+    g = torch.tensor([1., 4., 6., 4., 1.]) / 16
+    return torch.outer(g, g).to(device)
+
+
+def _lap_composed(sr, hr, levels):
+    """[N]: the same value from differentiable device ops in fp32 (what --second_order takes)."""
+    C = sr.shape[1]
+    k = _lap_window(sr.device).expand(C, 1, 5, 5)
+
+    def gauss(x, scale):
+        return torch.nn.functional.conv2d(torch.nn.functional.pad(x, (2, 2, 2, 2), mode='reflect'), k * scale, groups=C)
+    c = sr - hr
+    n0 = c[0].numel()
+    total = 0
+    for s in range(levels - 1):
+        down = gauss(c, 1.0)[:, :, ::2, ::2]
+        z = torch.zeros_like(c)
+        z[:, :, ::2, ::2] = down
+        total = total + 2.0 ** s * (c - gauss(z, 4.0)).abs().flatten(1).sum(1)
+        c = down
+    return (total + 2.0 ** (levels - 1) * c.abs().flatten(1).sum(1)) / n0
+
+
+def _lap_args(sr, hr, levels, what):
+    if sr.dim() != 4 or sr.shape != hr.shape:
+        raise ValueError("%s needs two [N,C,H,W] tensors of one shape, got %s, %s" % (what, tuple(sr.shape), tuple(hr.shape)))
+    if not isinstance(levels, int) or not 2 <= levels <= 5:
+        raise ValueError("%s: levels must be 2..5, got %r" % (what, levels))
+    h, w = sr.shape[2], sr.shape[3]
+    for _ in range(levels - 1):
+        if h < 3 or w < 3:
+            raise ValueError("%s: every filtered level needs both sides >= 3 (reflection by 2; H, W >= 17 for five levels), got %s with "
+                             "levels=%d" % (what, tuple(sr.shape), levels))
+        h, w = (h + 1) // 2, (w + 1) // 2
+    sr, hr = sr.contiguous(), hr.contiguous()
+    _hip.require_cuda(sr, hr)
+    return sr, hr
+
+
+def lap_loss(sr, hr, levels=LAP_LEVELS):
+    """Laplacian-pyramid L1 over the whole batch: sum_s 2^s sum |b_s(sr - hr)| / (N C H W), 5-tap binomial window, reflected borders,
+    the last level the low-pass residual.  Gradient for `sr` only."""
+    sr, hr = _lap_args(sr, hr, levels, "lap_loss")
+    if double_backward():
+        return _lap_composed(sr, hr, levels).mean()
+    return _LapLoss.apply(sr, hr, levels, True).reshape(())
+
+
+def lap_loss_per_sample(sr, hr, levels=LAP_LEVELS):
+    """[N,C,H,W] x [N,C,H,W] -> [N]: the same term for every sample on its own (tasks adapted in lockstep)."""
+    sr, hr = _lap_args(sr, hr, levels, "lap_loss_per_sample")
+    if double_backward():
+        return _lap_composed(sr, hr, levels)
+    return _LapLoss.apply(sr, hr, levels, False)
+
+
 def frames_to_u8(x):
     """x [N,C,H,W] (or [C,H,W], [H,W]) in unit range, C = 1 or 3 -> uint8 [N,H,W,C] ([H,W,C], [H,W]) on the device, quantised as
     utils.save_image does (the metric's device function): a frame leaves the device as bytes."""

@@ -1,4 +1,4 @@
-"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM, MSSSIM}.
+"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM, MSSSIM, Lap}.
 
 Surface follows the reference's ``Loss`` (loss.py:278-350): ``criterion(sr, hr) -> {TYPE: w*loss, ...,
 'total': sum}``.  L1 / MSE run on the fused savfi reduction kernel (one launch, no temporaries), SSIM on the fused
@@ -8,6 +8,10 @@ the reference's VGG / GAN / SuperSloMo terms are outside this path and are rejec
 MSSSIM is an ADDITION: the reference's ``Loss`` has no such branch, though the reference vendors ``pytorch_msssim.msssim``.  The term is
 ``1 - msssim(sr, hr, normalize=True)`` with the data-dependent range of every level, on the multi-scale kernels of csrc/ssim.hip.
 ``normalize=True`` because the plain product is NaN whenever a level's contrast mean is negative, which an untrained prediction gives.
+
+Lap is an ADDITION too: the Laplacian-pyramid L1 that kernel-based interpolators train with, five levels of the 5-tap binomial window
+with reflected borders, the last level the low-pass residual, ``sum_s 2^s sum |b_s| / n_0`` (the scale of L1), on the fused kernels of
+csrc/laploss.hip (one pyramid of ``sr - hr``; gradient for ``sr`` only).  Frames of 17 x 17 or more.
 """
 import torch.nn as nn
 
@@ -24,9 +28,9 @@ def msssim_loss_per_sample(sr, hr):
     return 1 - hip_ops.msssim_per_sample(sr, hr, normalize=True)
 
 
-_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss, 'MSSSIM': msssim_loss}
+_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss, 'MSSSIM': msssim_loss, 'Lap': hip_ops.lap_loss}
 _KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample, 'SSIM': hip_ops.ssim_loss_per_sample,
-                       'MSSSIM': msssim_loss_per_sample}
+                       'MSSSIM': msssim_loss_per_sample, 'Lap': hip_ops.lap_loss_per_sample}
 
 
 class Loss(nn.modules.loss._Loss):
