@@ -82,7 +82,8 @@ extern "C" {
  * savfi_conv3x3_tasks_pre_pool_f32; then savfi_filterinterp_fwd_slice_f32; then, for multi-scale
  * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32; then, for SepConv's second-order terms,
  * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form; then, for the Laplacian-pyramid loss term, savfi_laploss_scratch_bytes,
- * savfi_laploss_f32, savfi_laploss_bwd_f32. */
+ * savfi_laploss_f32, savfi_laploss_bwd_f32; then, for the census loss term, savfi_census_scratch_bytes, savfi_census_f32,
+ * savfi_census_bwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -441,6 +442,36 @@ int savfi_laploss_f32(const float* sr, const float* hr, float* result, void* scr
                       void* stream);
 int savfi_laploss_bwd_f32(const float* sr, const float* hr, const float* g_loss, void* scratch, float* g_sr, int rows, int C, int H,
                           int W, int levels, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Census (soft ternary) loss term `Census` and its gradient (csrc/census.hip), added under ABI 24.  `rows` independent losses per
+ * call, each the mean over `n` consecutive samples (n = 1: per sample; rows = 1, n = N: one value over a batch).
+ *   sr, hr [rows * n, C, H, W] (prediction, target), C = 3 or 1, H, W >= 3.  Per sample:
+ *     g = 0.2989 x_0 + 0.5870 x_1 + 0.1140 x_2 (C = 1: g = x_0), and g = 0 outside the frame (zero padding)
+ *     for the 49 offsets o in {-3..3}^2:   d_o(p) = g(p + o) - g(p)        t_o(p) = d_o / sqrt(0.81 + d_o^2)
+ *     delta_o = (t_o(sr) - t_o(hr))^2      h_o = delta_o / (0.1 + delta_o)   c(p) = sum_o h_o(p) / 49
+ *     census = sum_p m(p) c(p) / (H W),    m(p) = 1 for 1 <= y <= H - 2 and 1 <= x <= W - 2, else 0
+ *   result[r] = mean of census over the n samples of row r, fully overwritten.
+ *   Errors, checked in this order before any launch: SAVFI_E_NULL; SAVFI_E_SHAPE (a dimension <= 0, H or W below 3);
+ *   SAVFI_E_UNSUPPORTED (C not 1 or 3, an output pointer equal to an operand or to another output, a float pointer that is not 4-byte
+ *   aligned or a scratch that is not 8-byte aligned); SAVFI_E_TOOBIG (rows * n > 65535 or H * W >= 2^31).
+ *   Forward: one launch of 256-thread workgroups, one per tile of 8 rows x 32 columns per sample, one pixel per thread (the op is
+ *   bound by its arithmetic, not by staging: small tiles spread a 256 x 448 frame over 448 workgroups), which stage the 14 x 38 gray
+ *   patches of both images in LDS and leave one double each, and a finish launch.  Elements are fp32 (correctly rounded sqrt and
+ *   division); sums are carried in double.
+ *   `scratch`: savfi_census_scratch_bytes(rows, n, C, H, W) bytes, 16-byte aligned, caller-owned: one double per workgroup,
+ *     partial[((r * n + i) * ceil(H / 8) + ty) * ceil(W / 32) + tx] = sum over tile (ty, tx) of sample i of row r of m(p) sum_o h_o(p),
+ *   rows * n * ceil(H / 8) * ceil(W / 32) doubles, the total rounded up to a multiple of 16 bytes.  The finish adds a row's partials
+ *   in that order (thread-strided, then one butterfly) and divides by 49 n H W once.
+ *   bwd: ONE launch, nothing kept from the forward.  g_sr [rows * n, C, H, W] = g_loss[r] * d result[r] / d sr, every element written
+ *   once, recomputed from the same patches by the forward's device functions; hr gets no gradient.
+ *   No atomics, no cleared memory, no host read: capturable and bit-reproducible; an identical pair gives value 0 and gradient 0
+ *   exactly.  All global accesses are scalar 4-byte ones: operands 4 or 8 bytes off a 16-byte boundary give the same bits.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_census_scratch_bytes(int rows, int n, int C, int H, int W);
+int savfi_census_f32(const float* sr, const float* hr, float* result, void* scratch, int rows, int n, int C, int H, int W, void* stream);
+int savfi_census_bwd_f32(const float* sr, const float* hr, const float* g_loss, float* g_sr, int rows, int n, int C, int H, int W,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:

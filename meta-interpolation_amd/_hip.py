@@ -86,6 +86,9 @@ _PROTOTYPES = {
     "savfi_laploss_scratch_bytes": [c_int, c_int, c_int, c_int, c_int],
     "savfi_laploss_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_laploss_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "savfi_census_scratch_bytes": [c_int, c_int, c_int, c_int, c_int],
+    "savfi_census_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "savfi_census_bwd_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_fwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_bwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_workspace_floats": [c_int] * 7,

@@ -24,6 +24,9 @@ Additions for the MI355X build (all optional, all default to the reference behav
   --loss ...+w*MSSSIM          a term the reference's Loss has no branch for: 1 - msssim(sr, hr, normalize=True) on the fused multi-scale kernels
   --loss ...+w*Lap             another one: the Laplacian-pyramid L1 (five levels, 5-tap binomial window, reflected borders, low-pass residual last,
                                sum_s 2^s sum |b_s| / n_0) on the fused kernels of csrc/laploss.hip; frames of 17 x 17 or more
+  --loss ...+w*Census          another one: the census (soft ternary) loss, a distance between the 7 x 7 local-structure descriptors of the gray
+                               images (zero padding, outermost ring of pixels masked) on the fused kernels of csrc/census.hip; 3 or 1
+                               channels, frames of 3 x 3 or more; the constants presume unit-range frames
   --synthetic                  feed seeded synthetic septuplets instead of reading a dataset
 """
 import argparse

@@ -1088,6 +1088,93 @@ def lap_loss_per_sample(sr, hr, levels=LAP_LEVELS):
     return _LapLoss.apply(sr, hr, levels, False)
 
 
+# --------------------------------------------------------------------------------------------
+# Census (soft ternary) loss, the term 'Census' of --loss   (no counterpart in the reference; definition: include/savfi_hip.h)
+# --------------------------------------------------------------------------------------------
+class _CensusLoss(torch.autograd.Function):
+    """sr, hr [N,C,H,W] -> float32[N] (every sample on its own) or float32[1] (fold: the mean over the batch); capturable; deterministic."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, fold):
+        _hip.require_cuda(sr, hr)
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("census_loss differentiates w.r.t. the prediction only")
+        N, C, H, W = sr.shape
+        rows, n = (1, N) if fold else (N, 1)
+        res = torch.empty(rows, dtype=torch.float32, device=sr.device)
+        scratch = torch.empty(_workspace_floats("savfi_census_scratch_bytes", rows, n, C, H, W) // 8, dtype=torch.float64, device=sr.device)
+        lib = _hip.lib()
+        _hip.launch("census", lambda: _hip.check(lib.savfi_census_f32(
+            sr.data_ptr(), hr.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, n, C, H, W, _hip.current_stream()),
+            "savfi_census_f32"), nbytes=8 * sr.numel())
+        ctx.fold = fold
+        ctx.save_for_backward(sr, hr)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        sr, hr = ctx.saved_tensors
+        N, C, H, W = sr.shape
+        rows, n = (1, N) if ctx.fold else (N, 1)
+        g = g.contiguous()
+        gsr = torch.empty_like(sr)
+        lib = _hip.lib()
+        _hip.launch("census_bwd", lambda: _hip.check(lib.savfi_census_bwd_f32(
+            sr.data_ptr(), hr.data_ptr(), g.data_ptr(), gsr.data_ptr(), rows, n, C, H, W, _hip.current_stream()),
+            "savfi_census_bwd_f32"), nbytes=12 * sr.numel())
+        return gsr, None, None
+
+
+_CENSUS_GRAY = (0.2989, 0.5870, 0.1140)
+
+
+def _census_composed(sr, hr):
+    """[N]: the same value from differentiable device ops in fp32 (what --second_order takes): 49-channel tensors, as the definition reads."""
+    H, W = sr.shape[2], sr.shape[3]
+
+    def ternary(x):
+        g = x[:, 0] if x.shape[1] == 1 else _CENSUS_GRAY[0] * x[:, 0] + _CENSUS_GRAY[1] * x[:, 1] + _CENSUS_GRAY[2] * x[:, 2]
+        p = torch.nn.functional.pad(g, (3, 3, 3, 3))
+        d = torch.stack([p[:, dy:dy + H, dx:dx + W] for dy in range(7) for dx in range(7)], 1) - g[:, None]
+        return d / torch.sqrt(0.81 + d * d)
+    delta = (ternary(sr) - ternary(hr)) ** 2
+    c = (delta / (0.1 + delta)).mean(1)
+    return c[:, 1:-1, 1:-1].flatten(1).sum(1) / (H * W)
+
+
+def _census_args(sr, hr, what):
+    if sr.dim() != 4 or sr.shape != hr.shape:
+        raise ValueError("%s needs two [N,C,H,W] tensors of one shape, got %s, %s" % (what, tuple(sr.shape), tuple(hr.shape)))
+    if sr.shape[1] not in (1, 3):
+        raise ValueError("%s needs 3 channels (gray = 0.2989 R + 0.5870 G + 0.1140 B) or 1, got %s" % (what, tuple(sr.shape)))
+    if sr.shape[2] < 3 or sr.shape[3] < 3:
+        raise ValueError("%s needs H, W >= 3, got %s" % (what, tuple(sr.shape)))
+    sr, hr = sr.contiguous(), hr.contiguous()
+    _hip.require_cuda(sr, hr)
+    return sr, hr
+
+
+def census_loss(sr, hr):
+    """Census (soft ternary) loss as one value, the mean over the batch: per sample, with g the gray image (zero outside the frame),
+    d_o = g(p + o) - g(p) for the 49 offsets of the 7 x 7 window, t_o = d_o / sqrt(0.81 + d_o^2), delta_o = (t_o(sr) - t_o(hr))^2,
+    sum over the pixels off the outermost ring of mean_o delta_o / (0.1 + delta_o), divided by H W.  The constants presume unit-range
+    frames; the term is applied to whatever tensors it is handed (Super SloMo's mean-subtracted and VoxelFlow's normalised frames
+    included), as the other terms are.  Gradient for `sr` only."""
+    sr, hr = _census_args(sr, hr, "census_loss")
+    if double_backward():
+        return _census_composed(sr, hr).mean()
+    return _CensusLoss.apply(sr, hr, True).reshape(())
+
+
+def census_loss_per_sample(sr, hr):
+    """[N,C,H,W] x [N,C,H,W] -> [N]: the same term for every sample on its own (tasks adapted in lockstep)."""
+    sr, hr = _census_args(sr, hr, "census_loss_per_sample")
+    if double_backward():
+        return _census_composed(sr, hr)
+    return _CensusLoss.apply(sr, hr, False)
+
+
 def frames_to_u8(x):
     """x [N,C,H,W] (or [C,H,W], [H,W]) in unit range, C = 1 or 3 -> uint8 [N,H,W,C] ([H,W,C], [H,W]) on the device, quantised as
     utils.save_image does (the metric's device function): a frame leaves the device as bytes."""

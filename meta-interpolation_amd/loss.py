@@ -1,4 +1,4 @@
-"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM, MSSSIM, Lap}.
+"""Loss wrapper for the inner/outer objectives: ``'w*TYPE+w*TYPE'`` with TYPE in {L1, MSE, SSIM, MSSSIM, Lap, Census}.
 
 Surface follows the reference's ``Loss`` (loss.py:278-350): ``criterion(sr, hr) -> {TYPE: w*loss, ...,
 'total': sum}``.  L1 / MSE run on the fused savfi reduction kernel (one launch, no temporaries), SSIM on the fused
@@ -12,6 +12,14 @@ MSSSIM is an ADDITION: the reference's ``Loss`` has no such branch, though the r
 Lap is an ADDITION too: the Laplacian-pyramid L1 that kernel-based interpolators train with, five levels of the 5-tap binomial window
 with reflected borders, the last level the low-pass residual, ``sum_s 2^s sum |b_s| / n_0`` (the scale of L1), on the fused kernels of
 csrc/laploss.hip (one pyramid of ``sr - hr``; gradient for ``sr`` only).  Frames of 17 x 17 or more.
+
+Census is an ADDITION as well: the census (soft ternary) loss that flow-based interpolators train with, a distance between 7 x 7
+local-structure descriptors that a brightness or contrast change between the frames hardly moves.  On the gray image ``g`` (zero outside
+the frame), ``t_o = d_o / sqrt(0.81 + d_o^2)`` of ``d_o = g(p + o) - g(p)`` for the 49 offsets, ``delta_o = (t_o(sr) - t_o(hr))^2``, the mean
+over the offsets of ``delta_o / (0.1 + delta_o)``, summed over the pixels off the outermost ring and divided by ``H W``, on the fused kernels
+of csrc/census.hip (gradient for ``sr`` only).  3 or 1 channels, frames of 3 x 3 or more.  The constants presume unit-range frames; the
+term is applied to whatever tensors the criterion receives, as the other terms are -- Super SloMo's mean-subtracted and VoxelFlow's
+normalised frames included.
 """
 import torch.nn as nn
 
@@ -28,9 +36,10 @@ def msssim_loss_per_sample(sr, hr):
     return 1 - hip_ops.msssim_per_sample(sr, hr, normalize=True)
 
 
-_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss, 'MSSSIM': msssim_loss, 'Lap': hip_ops.lap_loss}
+_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss, 'MSSSIM': msssim_loss, 'Lap': hip_ops.lap_loss,
+            'Census': hip_ops.census_loss}
 _KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample, 'SSIM': hip_ops.ssim_loss_per_sample,
-                       'MSSSIM': msssim_loss_per_sample, 'Lap': hip_ops.lap_loss_per_sample}
+                       'MSSSIM': msssim_loss_per_sample, 'Lap': hip_ops.lap_loss_per_sample, 'Census': hip_ops.census_loss_per_sample}
 
 
 class Loss(nn.modules.loss._Loss):
