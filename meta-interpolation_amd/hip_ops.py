@@ -69,10 +69,17 @@ class _VoxelWarp(torch.autograd.Function):
 def _bilinear_border(img, cx, cy):
     """F.grid_sample(img, stack(cx, cy), bilinear, padding_mode='border', align_corners=True) written with gathers (ATen
     GridSampler.h: unnormalise, clip the coordinate, four corners): differentiable in `img`, `cx`, `cy` to any order --
-    ATen's grid_sampler_2d_backward has no derivative, so the fused op and F.grid_sample alike stop at first order."""
+    ATen's grid_sampler_2d_backward has no derivative, so the fused op and F.grid_sample alike stop at first order.
+    The clip has ATen's slope (clip_coordinates_set_grad), which is also the fused kernel's: zero for s <= 0 and s >= size - 1, the
+    bounds included, where clamp() alone would pass the gradient of a coordinate that sits exactly on a bound.  Inside the open interval
+    the coordinate itself goes on, so values and derivatives of every order there are what clamp() gave."""
     N, C, H, W = img.shape
-    ix = ((cx + 1.0) * 0.5 * (W - 1)).clamp(0, W - 1)
-    iy = ((cy + 1.0) * 0.5 * (H - 1)).clamp(0, H - 1)
+
+    def clip(s, size):
+        return torch.where((s > 0) & (s < size - 1), s, s.detach().clamp(0, size - 1))
+
+    ix = clip((cx + 1.0) * 0.5 * (W - 1), W)
+    iy = clip((cy + 1.0) * 0.5 * (H - 1), H)
     x0, y0 = ix.detach().floor(), iy.detach().floor()
     fx, fy = (ix - x0).unsqueeze(1), (iy - y0).unsqueeze(1)
     x0i, y0i = x0.long().clamp(0, W - 1), y0.long().clamp(0, H - 1)
