@@ -83,7 +83,7 @@ extern "C" {
  * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32; then, for SepConv's second-order terms,
  * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form; then, for the Laplacian-pyramid loss term, savfi_laploss_scratch_bytes,
  * savfi_laploss_f32, savfi_laploss_bwd_f32; then, for the census loss term, savfi_census_scratch_bytes, savfi_census_f32,
- * savfi_census_bwd_f32. */
+ * savfi_census_bwd_f32; then, for the second-order terms of the two warps, savfi_voxelwarp_bwd2_f32, savfi_flowwarp_bwd2_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -231,6 +231,16 @@ int savfi_voxelwarp_fwd_f32(const float* frames, const float* x3, float* out,
 int savfi_voxelwarp_bwd_f32(const float* frames, const float* x3, const float* gO,
                             float* g_x3, float* g_frames,
                             int B, int H, int W, void* stream);
+/* The backward of g_x3 above (second order, frames constant).  v [B,3,H,W] is the cotangent of g_x3.  Per pixel, with A. / B. the
+ * coordinate slopes of tap a (I0) / tap b (I1) -- (size-1)/2, 0 where the coordinate is clipped --, DX / DY the derivatives of a tap's
+ * sample by its source position and X the mixed difference of its four corners (both zero across a dropped upper corner):
+ *   d_gO [B,3,H,W] = 0.5 (v0 ((1-m) Bx DXb - m Ax DXa) + v1 ((1-m) By DYb - m Ay DYa) + v2 (o1 - o2))
+ *   d_x3 [B,3,H,W] = H v,  H00 = H11 = H22 = 0,  H01 = 0.25 sum_c gO (m Ax Ay Xa + (1-m) Bx By Xb),
+ *                    H02 = -0.25 sum_c gO (Ax DXa + Bx DXb),  H12 = -0.25 sum_c gO (Ay DYa + By DYb)
+ * Either output may be NULL (= not computed, not written), not both.  One launch, a gather: no atomics, no pre-zeroing, every element
+ * written once -- capturable and bit-reproducible.  Errors as savfi_voxelwarp_bwd_f32: SAVFI_E_NULL, SAVFI_E_SHAPE. */
+int savfi_voxelwarp_bwd2_f32(const float* frames, const float* x3, const float* gO, const float* v,
+                             float* d_gO, float* d_x3, int B, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * 2x2 / stride 2 average pooling of `planes` = N*C maps [H,W] -> [H/2,W/2] (floor): torch.nn.AvgPool2d(2, 2)
@@ -260,6 +270,16 @@ int savfi_avgpool2x2_bwd_fused_f32(const float* gout, const float* gskip, const 
 int savfi_flowwarp_fwd_f32(const float* img, const float* flow, float* out, int N, int C, int H, int W, void* stream);
 int savfi_flowwarp_bwd_f32(const float* img, const float* flow, const float* gout, float* gflow,
                            int N, int C, int H, int W, void* stream);
+/* The backward of the flow gradient above (second order, img constant).  v [N,2,H,W] = (vu, vv) is the cotangent of gflow; with
+ * Dx_c / Dy_c the derivatives of out[c] by the source position, X_c = (se - sw) - (ne - nw) the mixed difference of the cell's corners
+ * (corners outside the image count as zero) and sx = (W/2)*(2/W), sy = (H/2)*(2/H) in fp32 as the first order applies them:
+ *   d_gout [N,C,H,W] = vu sx Dx_c + vv sy Dy_c
+ *   d_flow [N,2,H,W] = (vv, vu) sx sy sum_c gout_c X_c            (the diagonal of the per-pixel Hessian is zero inside a cell)
+ * A pixel whose cell has no corner inside the image (far outside, NaN / inf flow) gets zeros in both.  Either output may be NULL (= not
+ * computed, not written), not both.  One launch, a gather: no atomics, no pre-zeroing, every element written once -- capturable and
+ * bit-reproducible.  Errors as savfi_flowwarp_bwd_f32: SAVFI_E_NULL, SAVFI_E_SHAPE, SAVFI_E_TOOBIG. */
+int savfi_flowwarp_bwd2_f32(const float* img, const float* flow, const float* gout, const float* v,
+                            float* d_gout, float* d_flow, int N, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Pixel (un)shuffle with the reference's channel order.

@@ -59,11 +59,13 @@ _PROTOTYPES = {
     "savfi_convk_dgrad_masked_f32": [_P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_voxelwarp_fwd_f32": [_P, _P, _P, c_int, c_int, c_int, _P],
     "savfi_voxelwarp_bwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P],
+    "savfi_voxelwarp_bwd2_f32": [_P] * 6 + [c_int, c_int, c_int, _P],
     "savfi_avgpool2x2_fwd_f32": [_P, _P, c_int64, c_int, c_int, _P],
     "savfi_avgpool2x2_bwd_f32": [_P, _P, c_int64, c_int, c_int, _P],
     "savfi_avgpool2x2_bwd_fused_f32": [_P, _P, _P, c_float, _P, c_int64, c_int, c_int, _P],
     "savfi_flowwarp_fwd_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_flowwarp_bwd_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P],
+    "savfi_flowwarp_bwd2_f32": [_P] * 6 + [c_int, c_int, c_int, c_int, _P],
     "savfi_pixel_unshuffle_f32": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_pixel_shuffle_f32": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_mt_update_f32": [c_int, c_int, c_int, _PP, _PP, _PP, _PP, _PP, _PP, _PP, _I64P, _FP, _FP,

@@ -21,6 +21,11 @@ Additions for the MI355X build (all optional, all default to the reference behav
   --sepconv_second_order {0,1} --model sepconv --second_order: 1 carries the second-order terms through the 51-tap op (FunctionSepconvTwice, a fused
                                second-backward kernel); default 0: the op's backward hands out graph-less gradients and they are dropped, as in the
                                reference.  Has effect only in second-order passes
+  --warp_second_order {0,1}    --second_order through the two warps: 1 makes the VoxelFlow tail (--model voxelflow) and the pixel-flow warp
+                               (--model rrin / superslomo) fused twice-differentiable ops (_VoxelWarpTwice, _FlowWarpTwice: one second-backward
+                               kernel each); default 0: the VoxelFlow tail is composed from ATen ops in second-order passes and the pixel-flow
+                               warp's backward is once differentiable (--second_order raises on those two models).  Has effect only in
+                               second-order passes
   --loss ...+w*MSSSIM          a term the reference's Loss has no branch for: 1 - msssim(sr, hr, normalize=True) on the fused multi-scale kernels
   --loss ...+w*Lap             another one: the Laplacian-pyramid L1 (five levels, 5-tap binomial window, reflected borders, low-pass residual last,
                                sum_s 2^s sum |b_s| / n_0) on the fused kernels of csrc/laploss.hip; frames of 17 x 17 or more
@@ -63,11 +68,12 @@ _FLAGS = {
         ('fuse_support_pairs', int, 1), ('fuse_conv_act', int, 1), ('graph_inner_loop', int, -1), ('sepconv_window', int, 1),
         ('task_streams', int, -1), ('wgrad_overlap', int, 0), ('task_batch', int, 8), ('lazy_logging', int, 1),
         ('dain_task_modes', int, 0), ('eval_msssim', int, 0), ('sepconv_second_order', int, 0),
+        ('warp_second_order', int, 0),
         ('synthetic', 'flag', False),
     ],
 }
 
-_CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1], 'sepconv_second_order': [0, 1]}
+_CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1], 'sepconv_second_order': [0, 1], 'warp_second_order': [0, 1]}
 
 
 def build_parser():

@@ -97,6 +97,50 @@ __global__ __launch_bounds__(256) void flowwarp_bwd(const float* __restrict__ im
   o[plane] = gy * ((float)H / 2.f) * (2.f / (float)H);
 }
 
+// The backward of flowwarp_bwd (second order, image constant).  out[:, y, x] depends on flow[:, y, x] alone: the Hessian of <gout, out>
+// in the flow is one 2 x 2 block per pixel with a zero diagonal (a cell is linear in each axis), so this is one thread per pixel with
+// the gathers of flowwarp_bwd and no atomics.  (vu, vv) = the cotangent of gflow, Dx / Dy the brackets of flowwarp_bwd,
+// X = (se - sw) - (ne - nw), sx = (W / 2) * (2 / W) and sy = (H / 2) * (2 / H) applied as flowwarp_bwd applies them:
+//   d_gout[c] = vu sx Dx_c + vv sy Dy_c        d_flow[0] = vv sx sy sum_c g_c X_c        d_flow[1] = vu sx sy sum_c g_c X_c
+// A cell with no corner inside the image (also NaN / inf flows) gives zeros in every output, as `any` does at first order.
+// Per pixel 4 floats of flow / v and C of gout in, C + 2 out, coalesced; 4 corners x C channels from L2 / L1.
+template <bool WANT_GO, bool WANT_F>
+__global__ __launch_bounds__(256) void flowwarp_bwd2(const float* __restrict__ img, const float* __restrict__ flow,
+                                                     const float* __restrict__ gout, const float* __restrict__ v,
+                                                     float* __restrict__ d_gout, float* __restrict__ d_flow, int C, int H, int W) {
+  const int x = blockIdx.x * TX + threadIdx.x;
+  const int y = blockIdx.y * TY + threadIdx.y, n = blockIdx.z;
+  if (x >= W || y >= H) return;
+  const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+  const float* f = flow + (size_t)n * 2 * plane + p;
+  const Corner c = source_cell(x, y, f[0], f[plane], H, W);
+  const bool any = inside(c.y0, c.x0, H, W) || inside(c.y0, c.x0 + 1, H, W) || inside(c.y0 + 1, c.x0, H, W) ||
+                   inside(c.y0 + 1, c.x0 + 1, H, W);
+  const float* vp = v + (size_t)n * 2 * plane + p;
+  // the cotangents times d ix / d u and d iy / d v, in the order flowwarp_bwd multiplies its sums
+  const float vu = any ? vp[0] * ((float)W / 2.f) * (2.f / (float)W) : 0.f;
+  const float vv = any ? vp[plane] * ((float)H / 2.f) * (2.f / (float)H) : 0.f;
+  float s = 0.f;
+  for (int ch = 0; ch < C; ++ch) {
+    const size_t o = ((size_t)n * C + ch) * plane + p;
+    if (!any) {
+      if (WANT_GO) d_gout[o] = 0.f;
+      continue;
+    }
+    const float* a = img + ((size_t)n * C + ch) * plane;
+    const float nw = texel(a, c.y0, c.x0, H, W), ne = texel(a, c.y0, c.x0 + 1, H, W);
+    const float sw = texel(a, c.y0 + 1, c.x0, H, W), se = texel(a, c.y0 + 1, c.x0 + 1, H, W);
+    if (WANT_GO)
+      d_gout[o] = vu * ((ne - nw) * (1.f - c.fy) + (se - sw) * c.fy) + vv * ((sw - nw) * (1.f - c.fx) + (se - ne) * c.fx);
+    if (WANT_F) s += gout[o] * ((se - sw) - (ne - nw));
+  }
+  if (WANT_F) {
+    float* o = d_flow + (size_t)n * 2 * plane + p;
+    o[0] = s * vv * ((float)W / 2.f) * (2.f / (float)W);
+    o[plane] = s * vu * ((float)H / 2.f) * (2.f / (float)H);
+  }
+}
+
 int check(const void* a, const void* b, const void* c, int N, int C, int H, int W) {
   if (!a || !b || !c) return SAVFI_E_NULL;
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return SAVFI_E_SHAPE;
@@ -118,5 +162,20 @@ extern "C" int savfi_flowwarp_bwd_f32(const float* img, const float* flow, const
   if (int e = check(img, flow, gflow, N, C, H, W)) return e;
   hipLaunchKernelGGL(flowwarp_bwd, dim3(savfi_cdiv(W, TX), savfi_cdiv(H, TY), N), dim3(TX, TY), 0, (hipStream_t)stream, img, flow, gout, gflow, C,
                      H, W);
+  return savfi_launch_status();
+}
+
+extern "C" int savfi_flowwarp_bwd2_f32(const float* img, const float* flow, const float* gout, const float* v, float* d_gout,
+                                       float* d_flow, int N, int C, int H, int W, void* stream) {
+  if (!v || (!d_gout && !d_flow)) return SAVFI_E_NULL;
+  if (int e = check(img, flow, gout, N, C, H, W)) return e;
+  const dim3 grid(savfi_cdiv(W, TX), savfi_cdiv(H, TY), N), block(TX, TY);
+  hipStream_t st = (hipStream_t)stream;
+  if (d_gout && d_flow)
+    hipLaunchKernelGGL((flowwarp_bwd2<true, true>), grid, block, 0, st, img, flow, gout, v, d_gout, d_flow, C, H, W);
+  else if (d_gout)
+    hipLaunchKernelGGL((flowwarp_bwd2<true, false>), grid, block, 0, st, img, flow, gout, v, d_gout, d_flow, C, H, W);
+  else
+    hipLaunchKernelGGL((flowwarp_bwd2<false, true>), grid, block, 0, st, img, flow, gout, v, d_gout, d_flow, C, H, W);
   return savfi_launch_status();
 }

@@ -18,7 +18,8 @@ from . import _hip
 # Set by the meta system for the duration of a forward with --second_order: ops whose hand-written backward
 # is not itself differentiable switch to composed device ops (losses) or refuse (voxel warp) instead of
 # silently dropping second-order terms.  (FunctionSepconv does drop them, exactly like the reference: SURVEY.md
-# section 0, fact 9; --sepconv_second_order 1 makes the SepConv plugin use FunctionSepconvTwice in such passes.)
+# section 0, fact 9; --sepconv_second_order 1 makes the SepConv plugin use FunctionSepconvTwice in such passes, and
+# --warp_second_order 1 makes voxel_warp_blend / flow_warp use the fused twice-differentiable _VoxelWarpTwice / _FlowWarpTwice.)
 # Per THREAD (tasks may be adapted on concurrent threads; two systems in one process must not flip each other's ops):
 # worker threads get the caller's value through meta_learning_system._run_tasks.
 _PASS = threading.local()
@@ -107,9 +108,95 @@ def _voxel_warp_composed(frames, x3):
     return mask * o1 + (1.0 - mask) * o2
 
 
+class _VoxelWarpGrad(torch.autograd.Function):
+    """(frames, x3, gO) -> g_x3: the backward of _VoxelWarpTwice as a function of its own, through the entry point _VoxelWarp.backward
+    uses.  Its backward is savfi_voxelwarp_bwd2_f32 (csrc/voxelwarp.hip) and is once differentiable: a third derivative raises."""
+
+    @staticmethod
+    def forward(ctx, frames, x3, gO):
+        B, _, H, W = frames.shape
+        gO = gO.contiguous()
+        _hip.require_cuda(gO)
+        g_x3 = torch.empty_like(x3)
+        lib = _hip.lib()
+        _hip.launch("voxelwarp_bwd", lambda: _hip.check(lib.savfi_voxelwarp_bwd_f32(
+            frames.data_ptr(), x3.data_ptr(), gO.data_ptr(), g_x3.data_ptr(), None, B, H, W, _hip.current_stream()),
+            "savfi_voxelwarp_bwd_f32"), nbytes=4 * 15 * B * H * W)
+        ctx.save_for_backward(frames, x3, gO)
+        return g_x3
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        frames, x3, gO = ctx.saved_tensors
+        B, _, H, W = frames.shape
+        _, need_x, need_g = ctx.needs_input_grad
+        if not (need_x or need_g):
+            return None, None, None
+        v = v.contiguous()
+        _hip.require_cuda(v)
+        d_x3 = torch.empty_like(x3) if need_x else None
+        d_gO = torch.empty_like(gO) if need_g else None
+        lib = _hip.lib()
+        p = lambda t: None if t is None else t.data_ptr()
+        _hip.launch("voxelwarp_bwd2", lambda: _hip.check(lib.savfi_voxelwarp_bwd2_f32(
+            frames.data_ptr(), x3.data_ptr(), gO.data_ptr(), v.data_ptr(), p(d_gO), p(d_x3), B, H, W, _hip.current_stream()),
+            "savfi_voxelwarp_bwd2_f32"), nbytes=voxel_warp_bwd2_bytes(B, H, W, need_g, need_x))
+        return None, d_x3, d_gO
+
+
+def voxel_warp_bwd2_bytes(B, H, W, want_gO=True, want_x3=True):
+    """HBM bytes of savfi_voxelwarp_bwd2_f32 if every operand is read / written exactly once: frames (6), x3, gO, v (3 each) and 3
+    floats per requested output"""
+    return 4 * B * H * W * (15 + 3 * int(want_gO) + 3 * int(want_x3))
+
+
+class _VoxelWarpTwice(torch.autograd.Function):
+    """_VoxelWarp for frames WITHOUT gradient, twice differentiable in x3 (--warp_second_order 1).  The forward and the first-order
+    gradient go through the entry points of _VoxelWarp: same bits.  The backward is itself an autograd.Function (_VoxelWarpGrad), so under
+    create_graph=True g_x3 carries a graph and the second-order terms of MAML reach the outer gradient through savfi_voxelwarp_bwd2_f32.
+    Frames that require grad are refused: the second-order terms of g_frames are not built, and a graph-less g_frames would drop them
+    silently."""
+
+    @staticmethod
+    def forward(ctx, frames, x3):
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("_VoxelWarpTwice: the frames require grad, and the second-order terms of their gradient are not "
+                                      "implemented (they would be dropped silently); the composed op differentiates them")
+        _hip.require_cuda(frames, x3)
+        B, six, H, W = frames.shape
+        assert six == 6 and x3.shape == (B, 3, H, W)
+        out = torch.empty((B, 3, H, W), dtype=frames.dtype, device=frames.device)
+        lib = _hip.lib()
+        _hip.launch("voxelwarp_fwd", lambda: _hip.check(lib.savfi_voxelwarp_fwd_f32(
+            frames.data_ptr(), x3.data_ptr(), out.data_ptr(), B, H, W, _hip.current_stream()),
+            "savfi_voxelwarp_fwd_f32"), nbytes=4 * 12 * B * H * W)
+        ctx.save_for_backward(frames, x3)
+        return out
+
+    @staticmethod
+    def backward(ctx, gO):
+        frames, x3 = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        return None, _VoxelWarpGrad.apply(frames, x3, gO)
+
+
+def set_warp_second_order(value):
+    """--warp_second_order 1: in second-order passes (double_backward()) the two warps are the fused twice-differentiable ops.  Per thread,
+    like set_double_backward."""
+    _PASS.warp_second_order = bool(value)
+
+
+def warp_second_order():
+    return getattr(_PASS, 'warp_second_order', False)
+
+
 def voxel_warp_blend(frames, x3):
     """frames [B,6,H,W] (I0|I1), x3 [B,3,H,W] = tanh(conv4) -> interpolated frame [B,3,H,W]."""
     if double_backward():
+        if warp_second_order() and x3.is_cuda:
+            return _VoxelWarpTwice.apply(frames.contiguous(), x3.contiguous())
         return _voxel_warp_composed(frames, x3)
     return _VoxelWarp.apply(frames.contiguous(), x3.contiguous())
 
@@ -283,9 +370,84 @@ class _FlowWarp(torch.autograd.Function):
         return None, gflow
 
 
+class _FlowWarpGrad(torch.autograd.Function):
+    """(img, flow, gout) -> gflow: the backward of _FlowWarpTwice as a function of its own, through the entry point _FlowWarp.backward
+    uses.  Its backward is savfi_flowwarp_bwd2_f32 (csrc/flowwarp.hip) and is once differentiable: a third derivative raises."""
+
+    @staticmethod
+    def forward(ctx, img, flow, gout):
+        N, C, H, W = img.shape
+        gout = gout.contiguous()
+        _hip.require_cuda(gout)
+        gflow = torch.empty_like(flow)
+        lib = _hip.lib()
+        _hip.launch("flowwarp_bwd", lambda: _hip.check(lib.savfi_flowwarp_bwd_f32(
+            img.data_ptr(), flow.data_ptr(), gout.data_ptr(), gflow.data_ptr(), N, C, H, W, _hip.current_stream()),
+            "savfi_flowwarp_bwd_f32"), nbytes=4 * N * H * W * (2 * C + 4))
+        ctx.save_for_backward(img, flow, gout)
+        return gflow
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        img, flow, gout = ctx.saved_tensors
+        N, C, H, W = img.shape
+        _, need_f, need_g = ctx.needs_input_grad
+        if not (need_f or need_g):
+            return None, None, None
+        v = v.contiguous()
+        _hip.require_cuda(v)
+        d_flow = torch.empty_like(flow) if need_f else None
+        d_gout = torch.empty_like(gout) if need_g else None
+        lib = _hip.lib()
+        p = lambda t: None if t is None else t.data_ptr()
+        _hip.launch("flowwarp_bwd2", lambda: _hip.check(lib.savfi_flowwarp_bwd2_f32(
+            img.data_ptr(), flow.data_ptr(), gout.data_ptr(), v.data_ptr(), p(d_gout), p(d_flow), N, C, H, W, _hip.current_stream()),
+            "savfi_flowwarp_bwd2_f32"), nbytes=flow_warp_bwd2_bytes(N, C, H, W, need_g, need_f))
+        return None, d_flow, d_gout
+
+
+def flow_warp_bwd2_bytes(N, C, H, W, want_gout=True, want_flow=True):
+    """HBM bytes of savfi_flowwarp_bwd2_f32 if every operand is read / written exactly once: img and gout (C each), flow and v (2
+    each), C floats of d_gout and 2 of d_flow where requested"""
+    return 4 * N * H * W * (2 * C + 4 + C * int(want_gout) + 2 * int(want_flow))
+
+
+class _FlowWarpTwice(torch.autograd.Function):
+    """_FlowWarp, twice differentiable in the flow (--warp_second_order 1).  The forward and the first-order gradient go through the entry
+    points of _FlowWarp: same bits.  The backward is itself an autograd.Function (_FlowWarpGrad), so under create_graph=True gflow carries
+    a graph and the second-order terms of MAML reach the outer gradient through savfi_flowwarp_bwd2_f32.  An image that requires grad is
+    refused, as _FlowWarp refuses it."""
+
+    @staticmethod
+    def forward(ctx, img, flow):
+        _hip.require_cuda(img, flow)
+        N, C, H, W = img.shape
+        assert flow.shape == (N, 2, H, W), (img.shape, flow.shape)
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("flow_warp differentiates w.r.t. the flow only: on the reference's path the warped "
+                                      "images are network inputs (superslomo/model.py:600-624, rrin/model.py:99-100)")
+        out = torch.empty_like(img)
+        lib = _hip.lib()
+        _hip.launch("flowwarp_fwd", lambda: _hip.check(lib.savfi_flowwarp_fwd_f32(
+            img.data_ptr(), flow.data_ptr(), out.data_ptr(), N, C, H, W, _hip.current_stream()),
+            "savfi_flowwarp_fwd_f32"), nbytes=4 * N * H * W * (2 * C + 2))
+        ctx.save_for_backward(img, flow)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        img, flow = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        return None, _FlowWarpGrad.apply(img, flow, gout)
+
+
 def flow_warp(img, flow):
     """img [N,C,H,W] sampled at (x + u - 0.5, y + v - 0.5), flow = (u, v) [N,2,H,W] in pixels: exactly what
     backWarp / warp of the reference compute (their normalisation under grid_sample's align_corners=False)."""
+    if double_backward() and warp_second_order() and flow.is_cuda:
+        return _FlowWarpTwice.apply(img.contiguous(), flow.contiguous())
     return _FlowWarp.apply(img.contiguous(), flow.contiguous())
 
 

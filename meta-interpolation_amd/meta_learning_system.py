@@ -685,13 +685,14 @@ class SceneAdaptiveInterpolation(nn.Module):
         streams = self._task_stream_pool[:n]
         cur = torch.cuda.current_stream(dev_index)
         results, errors = {}, []
-        flags = (hip_ops.double_backward(), model_utils.fuse_conv_act())
+        flags = (hip_ops.double_backward(), model_utils.fuse_conv_act(), hip_ops.warp_second_order())
 
         def worker(i):
             try:
                 torch.cuda.set_device(dev_index)                # new threads start on device 0
                 hip_ops.set_double_backward(flags[0])           # per-thread switches: inherit the caller's
                 model_utils.set_fuse_conv_act(flags[1])
+                hip_ops.set_warp_second_order(flags[2])
                 with torch.cuda.stream(streams[i]):
                     for t in local[i::n]:
                         results[t] = body(t)
@@ -778,6 +779,8 @@ class SceneAdaptiveInterpolation(nn.Module):
     def _set_pass_flags(self, use_second_order):
         """Per-pass switches of the op layer (thread-local there: task threads inherit them through _run_tasks)."""
         hip_ops.set_double_backward(bool(use_second_order))
+        # --warp_second_order 1: the warps' fused twice-differentiable ops (they look at it in second-order passes only)
+        hip_ops.set_warp_second_order(bool(int(getattr(self.args, 'warp_second_order', 0) or 0)))
         self._first_order = not use_second_order
         # fused conv epilogues: first-order only (their backward is not differentiable)
         model_utils.set_fuse_conv_act(bool(getattr(self.args, 'fuse_conv_act', 0)) and not use_second_order)
