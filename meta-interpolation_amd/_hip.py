@@ -336,3 +336,15 @@ def launch(name, fn, nbytes=0, flops=0):
         fn()
     else:
         TIMER.launch(name, fn, nbytes, flops)
+
+
+def call(name, symbol, *args, nbytes=0, flops=0, stream=None):
+    """Launch the C entry point `symbol` under the timer name `name`: how every op runs a kernel.  A tensor argument goes as its
+    data_ptr(), None as NULL, anything else as it is (ints, floats, the host arrays of ptr_array / i64_array / f32_array, raw pointer
+    sums); the stream comes last -- torch's current one, read when the launch runs, unless `stream` (a raw handle) names another.  The
+    return code is checked under the symbol's own name, and the launch goes through launch() (looked up at call time: tests and tools
+    put a recorder in its place), so launch() and KernelTimer stay the one way to time it."""
+    import torch
+    entry = getattr(lib(), symbol)
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    launch(name, lambda: check(entry(*argv, current_stream() if stream is None else stream), symbol), nbytes=nbytes, flops=flops)

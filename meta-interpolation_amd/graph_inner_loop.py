@@ -311,7 +311,6 @@ class OuterGradAccumulator:
         rule = gl.rule
         dirs = gl.step_out[t]['dir']
         scale = -1.0 if gl.rule_id == _hip.RULE_SGD else 1.0
-        lib = _hip.lib()
         n = len(gl.routed)
         numel = [x.numel() for x in suffix]
         gos = [x.contiguous() for x in suffix]
@@ -320,9 +319,8 @@ class OuterGradAccumulator:
             outs = [dst[i] for i in range(n)]
         else:
             outs = [torch.empty_like(x) for x in gos]
-        args = (rule.lr_mode, n, _hip.ptr_array(gos), _hip.ptr_array(dirs), _hip.ptr_array(outs), _hip.i64_array(numel),
-                scale, _hip.current_stream())
-        _hip.launch("mt_update_bwd", lambda: _hip.check(lib.savfi_mt_update_bwd_f32(*args), "savfi_mt_update_bwd_f32"))
+        _hip.call("mt_update_bwd", "savfi_mt_update_bwd_f32", rule.lr_mode, n, _hip.ptr_array(gos), _hip.ptr_array(dirs), _hip.ptr_array(outs),
+                  _hip.i64_array(numel), scale)
         lr_keys = [k.replace(".", "-") for k in gl.routed]
         if rule.lr_mode == _hip.LR_SCALAR:
             # one row of per-tensor scalars per inner step; scattered into the lr parameters' .grad by install()

@@ -36,17 +36,31 @@ def double_backward():
 # --------------------------------------------------------------------------------------------
 # VoxelFlow warp + blend            (reference: voxelflow/core/models/voxel_flow.py:471-509)
 # --------------------------------------------------------------------------------------------
+def _voxelwarp_fwd(frames, x3):
+    """savfi_voxelwarp_fwd_f32: the one forward launch of _VoxelWarp and _VoxelWarpTwice."""
+    _hip.require_cuda(frames, x3)
+    B, six, H, W = frames.shape
+    assert six == 6 and x3.shape == (B, 3, H, W)
+    out = torch.empty((B, 3, H, W), dtype=frames.dtype, device=frames.device)
+    _hip.call("voxelwarp_fwd", "savfi_voxelwarp_fwd_f32", frames, x3, out, B, H, W, nbytes=4 * 12 * B * H * W)
+    return out
+
+
+def _voxelwarp_grads(frames, x3, gO, want_frames):
+    """savfi_voxelwarp_bwd_f32: the one first-order gradient launch of _VoxelWarp and _VoxelWarpGrad -> (g_x3, g_frames or None)."""
+    B, _, H, W = frames.shape
+    gO = gO.contiguous()
+    _hip.require_cuda(gO)
+    g_x3 = torch.empty_like(x3)
+    g_fr = torch.zeros_like(frames) if want_frames else None
+    _hip.call("voxelwarp_bwd", "savfi_voxelwarp_bwd_f32", frames, x3, gO, g_x3, g_fr, B, H, W, nbytes=4 * 15 * B * H * W)
+    return g_x3, g_fr
+
+
 class _VoxelWarp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, frames, x3):
-        _hip.require_cuda(frames, x3)
-        B, six, H, W = frames.shape
-        assert six == 6 and x3.shape == (B, 3, H, W)
-        out = torch.empty((B, 3, H, W), dtype=frames.dtype, device=frames.device)
-        lib = _hip.lib()
-        _hip.launch("voxelwarp_fwd", lambda: _hip.check(lib.savfi_voxelwarp_fwd_f32(
-            frames.data_ptr(), x3.data_ptr(), out.data_ptr(), B, H, W, _hip.current_stream()),
-            "savfi_voxelwarp_fwd_f32"), nbytes=4 * 12 * B * H * W)
+        out = _voxelwarp_fwd(frames, x3)
         ctx.save_for_backward(frames, x3)
         return out
 
@@ -54,16 +68,8 @@ class _VoxelWarp(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gO):
         frames, x3 = ctx.saved_tensors
-        B, _, H, W = frames.shape
-        gO = gO.contiguous()
         need_f, need_x = ctx.needs_input_grad
-        g_x3 = torch.empty_like(x3)
-        g_fr = torch.zeros_like(frames) if need_f else None
-        lib = _hip.lib()
-        _hip.launch("voxelwarp_bwd", lambda: _hip.check(lib.savfi_voxelwarp_bwd_f32(
-            frames.data_ptr(), x3.data_ptr(), gO.data_ptr(), g_x3.data_ptr(),
-            None if g_fr is None else g_fr.data_ptr(), B, H, W, _hip.current_stream()),
-            "savfi_voxelwarp_bwd_f32"), nbytes=4 * 15 * B * H * W)
+        g_x3, g_fr = _voxelwarp_grads(frames, x3, gO, need_f)
         return g_fr, (g_x3 if need_x else None)
 
 
@@ -109,19 +115,13 @@ def _voxel_warp_composed(frames, x3):
 
 
 class _VoxelWarpGrad(torch.autograd.Function):
-    """(frames, x3, gO) -> g_x3: the backward of _VoxelWarpTwice as a function of its own, through the entry point _VoxelWarp.backward
-    uses.  Its backward is savfi_voxelwarp_bwd2_f32 (csrc/voxelwarp.hip) and is once differentiable: a third derivative raises."""
+    """(frames, x3, gO) -> g_x3: the backward of _VoxelWarpTwice as a function of its own, through the launch _VoxelWarp.backward
+    runs (_voxelwarp_grads).  Its backward is savfi_voxelwarp_bwd2_f32 (csrc/voxelwarp.hip) and is once differentiable: a third derivative raises."""
 
     @staticmethod
     def forward(ctx, frames, x3, gO):
-        B, _, H, W = frames.shape
         gO = gO.contiguous()
-        _hip.require_cuda(gO)
-        g_x3 = torch.empty_like(x3)
-        lib = _hip.lib()
-        _hip.launch("voxelwarp_bwd", lambda: _hip.check(lib.savfi_voxelwarp_bwd_f32(
-            frames.data_ptr(), x3.data_ptr(), gO.data_ptr(), g_x3.data_ptr(), None, B, H, W, _hip.current_stream()),
-            "savfi_voxelwarp_bwd_f32"), nbytes=4 * 15 * B * H * W)
+        g_x3, _ = _voxelwarp_grads(frames, x3, gO, False)
         ctx.save_for_backward(frames, x3, gO)
         return g_x3
 
@@ -137,11 +137,8 @@ class _VoxelWarpGrad(torch.autograd.Function):
         _hip.require_cuda(v)
         d_x3 = torch.empty_like(x3) if need_x else None
         d_gO = torch.empty_like(gO) if need_g else None
-        lib = _hip.lib()
-        p = lambda t: None if t is None else t.data_ptr()
-        _hip.launch("voxelwarp_bwd2", lambda: _hip.check(lib.savfi_voxelwarp_bwd2_f32(
-            frames.data_ptr(), x3.data_ptr(), gO.data_ptr(), v.data_ptr(), p(d_gO), p(d_x3), B, H, W, _hip.current_stream()),
-            "savfi_voxelwarp_bwd2_f32"), nbytes=voxel_warp_bwd2_bytes(B, H, W, need_g, need_x))
+        _hip.call("voxelwarp_bwd2", "savfi_voxelwarp_bwd2_f32", frames, x3, gO, v, d_gO, d_x3, B, H, W,
+                  nbytes=voxel_warp_bwd2_bytes(B, H, W, need_g, need_x))
         return None, d_x3, d_gO
 
 
@@ -153,7 +150,7 @@ def voxel_warp_bwd2_bytes(B, H, W, want_gO=True, want_x3=True):
 
 class _VoxelWarpTwice(torch.autograd.Function):
     """_VoxelWarp for frames WITHOUT gradient, twice differentiable in x3 (--warp_second_order 1).  The forward and the first-order
-    gradient go through the entry points of _VoxelWarp: same bits.  The backward is itself an autograd.Function (_VoxelWarpGrad), so under
+    gradient are the launches of _VoxelWarp (_voxelwarp_fwd, _voxelwarp_grads): same bits.  The backward is itself an autograd.Function (_VoxelWarpGrad), so under
     create_graph=True g_x3 carries a graph and the second-order terms of MAML reach the outer gradient through savfi_voxelwarp_bwd2_f32.
     Frames that require grad are refused: the second-order terms of g_frames are not built, and a graph-less g_frames would drop them
     silently."""
@@ -163,14 +160,7 @@ class _VoxelWarpTwice(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("_VoxelWarpTwice: the frames require grad, and the second-order terms of their gradient are not "
                                       "implemented (they would be dropped silently); the composed op differentiates them")
-        _hip.require_cuda(frames, x3)
-        B, six, H, W = frames.shape
-        assert six == 6 and x3.shape == (B, 3, H, W)
-        out = torch.empty((B, 3, H, W), dtype=frames.dtype, device=frames.device)
-        lib = _hip.lib()
-        _hip.launch("voxelwarp_fwd", lambda: _hip.check(lib.savfi_voxelwarp_fwd_f32(
-            frames.data_ptr(), x3.data_ptr(), out.data_ptr(), B, H, W, _hip.current_stream()),
-            "savfi_voxelwarp_fwd_f32"), nbytes=4 * 12 * B * H * W)
+        out = _voxelwarp_fwd(frames, x3)
         ctx.save_for_backward(frames, x3)
         return out
 
@@ -204,18 +194,20 @@ def voxel_warp_blend(frames, x3):
 # --------------------------------------------------------------------------------------------
 # 2x2 average pooling          (reference: sepconv/model.py:176-187, rrin/unet.py:146, superslomo/model.py:66)
 # --------------------------------------------------------------------------------------------
+def _avgpool2x2_fwd_launch(x):
+    """savfi_avgpool2x2_fwd_f32 on a contiguous device map, no autograd"""
+    N, C, H, W = x.shape
+    out = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
+    _hip.call("avgpool2x2_fwd", "savfi_avgpool2x2_fwd_f32", x, out, N * C, H, W, nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
+    return out
+
+
 class _AvgPool2x2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _hip.require_cuda(x)
-        N, C, H, W = x.shape
-        out = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
-        lib = _hip.lib()
-        _hip.launch("avgpool2x2_fwd", lambda: _hip.check(lib.savfi_avgpool2x2_fwd_f32(
-            x.data_ptr(), out.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_fwd_f32"),
-            nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
-        ctx.hw = (H, W)
-        return out
+        ctx.hw = tuple(x.shape[2:])
+        return _avgpool2x2_fwd_launch(x)
 
     @staticmethod
     def backward(ctx, g):
@@ -231,26 +223,12 @@ class _AvgPool2x2Adjoint(torch.autograd.Function):
         N, C = g.shape[:2]
         H, W = hw
         gin = torch.empty((N, C, H, W), dtype=g.dtype, device=g.device)
-        lib = _hip.lib()
-        _hip.launch("avgpool2x2_bwd", lambda: _hip.check(lib.savfi_avgpool2x2_bwd_f32(
-            g.data_ptr(), gin.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_bwd_f32"),
-            nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
+        _hip.call("avgpool2x2_bwd", "savfi_avgpool2x2_bwd_f32", g, gin, N * C, H, W, nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
         return gin
 
     @staticmethod
     def backward(ctx, gg):
         return _AvgPool2x2.apply(gg.contiguous()), None
-
-
-def _avgpool2x2_fwd_launch(x):
-    """savfi_avgpool2x2_fwd_f32 on a contiguous device map, no autograd"""
-    N, C, H, W = x.shape
-    out = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
-    lib = _hip.lib()
-    _hip.launch("avgpool2x2_fwd", lambda: _hip.check(lib.savfi_avgpool2x2_fwd_f32(
-        x.data_ptr(), out.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_fwd_f32"),
-        nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
-    return out
 
 
 def _avgpool2x2_skip_adjoint(g_pool, g_skip, x, in_slope):
@@ -260,12 +238,9 @@ def _avgpool2x2_skip_adjoint(g_pool, g_skip, x, in_slope):
     g_pool = None if g_pool is None else g_pool.contiguous()
     g_skip = None if g_skip is None else g_skip.contiguous()
     gin = torch.empty_like(x)
-    lib = _hip.lib()
-    _hip.launch("avgpool2x2_bwd", lambda: _hip.check(lib.savfi_avgpool2x2_bwd_fused_f32(
-        None if g_pool is None else g_pool.data_ptr(), None if g_skip is None else g_skip.data_ptr(),
-        None if in_slope is None else x.data_ptr(), 1.0 if in_slope is None else float(in_slope), gin.data_ptr(),
-        N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_bwd_fused_f32"),
-        nbytes=4 * N * C * (H * W * (2 + (g_skip is not None)) + (H // 2) * (W // 2)))
+    _hip.call("avgpool2x2_bwd", "savfi_avgpool2x2_bwd_fused_f32", g_pool, g_skip, None if in_slope is None else x,
+              1.0 if in_slope is None else float(in_slope), gin, N * C, H, W,
+              nbytes=4 * N * C * (H * W * (2 + (g_skip is not None)) + (H // 2) * (W // 2)))
     return gin
 
 
@@ -277,12 +252,7 @@ class _AvgPool2x2AndSkip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, in_slope):
         _hip.require_cuda(x)
-        N, C, H, W = x.shape
-        out = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
-        lib = _hip.lib()
-        _hip.launch("avgpool2x2_fwd", lambda: _hip.check(lib.savfi_avgpool2x2_fwd_f32(
-            x.data_ptr(), out.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_fwd_f32"),
-            nbytes=4 * N * C * (H * W + (H // 2) * (W // 2)))
+        out = _avgpool2x2_fwd_launch(x)
         ctx.in_slope = in_slope
         ctx.save_for_backward(x)
         ctx.set_materialize_grads(False)
@@ -294,17 +264,7 @@ class _AvgPool2x2AndSkip(torch.autograd.Function):
         if g_pool is None and g_skip is None:
             return None, None
         x, = ctx.saved_tensors
-        N, C, H, W = x.shape
-        g_pool = None if g_pool is None else g_pool.contiguous()
-        g_skip = None if g_skip is None else g_skip.contiguous()
-        gin = torch.empty_like(x)
-        lib = _hip.lib()
-        _hip.launch("avgpool2x2_bwd", lambda: _hip.check(lib.savfi_avgpool2x2_bwd_fused_f32(
-            None if g_pool is None else g_pool.data_ptr(), None if g_skip is None else g_skip.data_ptr(),
-            None if ctx.in_slope is None else x.data_ptr(), 1.0 if ctx.in_slope is None else float(ctx.in_slope), gin.data_ptr(),
-            N * C, H, W, _hip.current_stream()), "savfi_avgpool2x2_bwd_fused_f32"),
-            nbytes=4 * N * C * (H * W * (2 + (g_skip is not None)) + (H // 2) * (W // 2)))
-        return gin, None
+        return _avgpool2x2_skip_adjoint(g_pool, g_skip, x, ctx.in_slope), None
 
 
 def avg_pool2x2_and_skip(x, in_slope=None):
@@ -339,6 +299,23 @@ class AvgPool2x2(torch.nn.Module):
 # --------------------------------------------------------------------------------------------
 # Backward warp by a pixel-unit flow    (reference: superslomo/model.py:231-307, rrin/model.py:8-20)
 # --------------------------------------------------------------------------------------------
+def _flowwarp_fwd(img, flow):
+    """savfi_flowwarp_fwd_f32: the one forward launch of _FlowWarp and _FlowWarpTwice (which check their arguments themselves)."""
+    N, C, H, W = img.shape
+    out = torch.empty_like(img)
+    _hip.call("flowwarp_fwd", "savfi_flowwarp_fwd_f32", img, flow, out, N, C, H, W, nbytes=4 * N * H * W * (2 * C + 2))
+    return out
+
+
+def _flowwarp_grad(img, flow, gout):
+    """savfi_flowwarp_bwd_f32: the one first-order gradient launch of _FlowWarp and _FlowWarpGrad -> gflow (gout contiguous)."""
+    N, C, H, W = img.shape
+    _hip.require_cuda(gout)
+    gflow = torch.empty_like(flow)
+    _hip.call("flowwarp_bwd", "savfi_flowwarp_bwd_f32", img, flow, gout, gflow, N, C, H, W, nbytes=4 * N * H * W * (2 * C + 4))
+    return gflow
+
+
 class _FlowWarp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, flow):
@@ -348,11 +325,7 @@ class _FlowWarp(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("flow_warp differentiates w.r.t. the flow only: on the reference's path the warped "
                                       "images are network inputs (superslomo/model.py:600-624, rrin/model.py:99-100)")
-        out = torch.empty_like(img)
-        lib = _hip.lib()
-        _hip.launch("flowwarp_fwd", lambda: _hip.check(lib.savfi_flowwarp_fwd_f32(
-            img.data_ptr(), flow.data_ptr(), out.data_ptr(), N, C, H, W, _hip.current_stream()),
-            "savfi_flowwarp_fwd_f32"), nbytes=4 * N * H * W * (2 * C + 2))
+        out = _flowwarp_fwd(img, flow)
         ctx.save_for_backward(img, flow)
         return out
 
@@ -360,30 +333,18 @@ class _FlowWarp(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gout):
         img, flow = ctx.saved_tensors
-        N, C, H, W = img.shape
-        gout = gout.contiguous()
-        gflow = torch.empty_like(flow)
-        lib = _hip.lib()
-        _hip.launch("flowwarp_bwd", lambda: _hip.check(lib.savfi_flowwarp_bwd_f32(
-            img.data_ptr(), flow.data_ptr(), gout.data_ptr(), gflow.data_ptr(), N, C, H, W, _hip.current_stream()),
-            "savfi_flowwarp_bwd_f32"), nbytes=4 * N * H * W * (2 * C + 4))
-        return None, gflow
+        return None, _flowwarp_grad(img, flow, gout.contiguous())
 
 
 class _FlowWarpGrad(torch.autograd.Function):
-    """(img, flow, gout) -> gflow: the backward of _FlowWarpTwice as a function of its own, through the entry point _FlowWarp.backward
-    uses.  Its backward is savfi_flowwarp_bwd2_f32 (csrc/flowwarp.hip) and is once differentiable: a third derivative raises."""
+    """(img, flow, gout) -> gflow: the backward of _FlowWarpTwice as a function of its own, through the launch _FlowWarp.backward
+    runs (_flowwarp_grad).  Its backward is savfi_flowwarp_bwd2_f32 (csrc/flowwarp.hip) and is once differentiable: a third derivative
+    raises."""
 
     @staticmethod
     def forward(ctx, img, flow, gout):
-        N, C, H, W = img.shape
         gout = gout.contiguous()
-        _hip.require_cuda(gout)
-        gflow = torch.empty_like(flow)
-        lib = _hip.lib()
-        _hip.launch("flowwarp_bwd", lambda: _hip.check(lib.savfi_flowwarp_bwd_f32(
-            img.data_ptr(), flow.data_ptr(), gout.data_ptr(), gflow.data_ptr(), N, C, H, W, _hip.current_stream()),
-            "savfi_flowwarp_bwd_f32"), nbytes=4 * N * H * W * (2 * C + 4))
+        gflow = _flowwarp_grad(img, flow, gout)
         ctx.save_for_backward(img, flow, gout)
         return gflow
 
@@ -399,11 +360,8 @@ class _FlowWarpGrad(torch.autograd.Function):
         _hip.require_cuda(v)
         d_flow = torch.empty_like(flow) if need_f else None
         d_gout = torch.empty_like(gout) if need_g else None
-        lib = _hip.lib()
-        p = lambda t: None if t is None else t.data_ptr()
-        _hip.launch("flowwarp_bwd2", lambda: _hip.check(lib.savfi_flowwarp_bwd2_f32(
-            img.data_ptr(), flow.data_ptr(), gout.data_ptr(), v.data_ptr(), p(d_gout), p(d_flow), N, C, H, W, _hip.current_stream()),
-            "savfi_flowwarp_bwd2_f32"), nbytes=flow_warp_bwd2_bytes(N, C, H, W, need_g, need_f))
+        _hip.call("flowwarp_bwd2", "savfi_flowwarp_bwd2_f32", img, flow, gout, v, d_gout, d_flow, N, C, H, W,
+                  nbytes=flow_warp_bwd2_bytes(N, C, H, W, need_g, need_f))
         return None, d_flow, d_gout
 
 
@@ -414,8 +372,8 @@ def flow_warp_bwd2_bytes(N, C, H, W, want_gout=True, want_flow=True):
 
 
 class _FlowWarpTwice(torch.autograd.Function):
-    """_FlowWarp, twice differentiable in the flow (--warp_second_order 1).  The forward and the first-order gradient go through the entry
-    points of _FlowWarp: same bits.  The backward is itself an autograd.Function (_FlowWarpGrad), so under create_graph=True gflow carries
+    """_FlowWarp, twice differentiable in the flow (--warp_second_order 1).  The forward and the first-order gradient are the launches
+    of _FlowWarp (_flowwarp_fwd, _flowwarp_grad): same bits.  The backward is itself an autograd.Function (_FlowWarpGrad), so under create_graph=True gflow carries
     a graph and the second-order terms of MAML reach the outer gradient through savfi_flowwarp_bwd2_f32.  An image that requires grad is
     refused, as _FlowWarp refuses it."""
 
@@ -427,11 +385,7 @@ class _FlowWarpTwice(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("flow_warp differentiates w.r.t. the flow only: on the reference's path the warped "
                                       "images are network inputs (superslomo/model.py:600-624, rrin/model.py:99-100)")
-        out = torch.empty_like(img)
-        lib = _hip.lib()
-        _hip.launch("flowwarp_fwd", lambda: _hip.check(lib.savfi_flowwarp_fwd_f32(
-            img.data_ptr(), flow.data_ptr(), out.data_ptr(), N, C, H, W, _hip.current_stream()),
-            "savfi_flowwarp_fwd_f32"), nbytes=4 * N * H * W * (2 * C + 2))
+        out = _flowwarp_fwd(img, flow)
         ctx.save_for_backward(img, flow)
         return out
 
@@ -457,17 +411,14 @@ def flow_warp(img, flow):
 def _launch_shuffle(x, r, down):
     _hip.require_cuda(x)
     B, C, H, W = x.shape
-    lib = _hip.lib()
     if down:
         assert H % r == 0 and W % r == 0
         out = torch.empty((B, C * r * r, H // r, W // r), dtype=x.dtype, device=x.device)
-        _hip.launch("pixel_unshuffle", lambda: _hip.check(lib.savfi_pixel_unshuffle_f32(
-            x.data_ptr(), out.data_ptr(), B, C, H, W, r, _hip.current_stream()), "savfi_pixel_unshuffle_f32"), nbytes=8 * x.numel())
+        _hip.call("pixel_unshuffle", "savfi_pixel_unshuffle_f32", x, out, B, C, H, W, r, nbytes=8 * x.numel())
     else:
         assert C % (r * r) == 0
         out = torch.empty((B, C // (r * r), H * r, W * r), dtype=x.dtype, device=x.device)
-        _hip.launch("pixel_shuffle", lambda: _hip.check(lib.savfi_pixel_shuffle_f32(
-            x.data_ptr(), out.data_ptr(), B, C, H, W, r, _hip.current_stream()), "savfi_pixel_shuffle_f32"), nbytes=8 * x.numel())
+        _hip.call("pixel_shuffle", "savfi_pixel_shuffle_f32", x, out, B, C, H, W, r, nbytes=8 * x.numel())
     return out
 
 
@@ -510,10 +461,7 @@ class _SubMean(torch.autograd.Function):
         out = torch.empty_like(x)
         mean = torch.empty((N, C, 1, 1), dtype=x.dtype, device=x.device)
         ws = torch.empty(_workspace_floats("savfi_sub_mean_workspace_floats", N * C, H * W), dtype=x.dtype, device=x.device)
-        lib = _hip.lib()
-        _hip.launch("sub_mean", lambda: _hip.check(lib.savfi_sub_mean_f32(
-            x.data_ptr(), out.data_ptr(), mean.data_ptr(), ws.data_ptr(), N * C, H * W, _hip.current_stream()), "savfi_sub_mean_f32"),
-            nbytes=12 * x.numel())
+        _hip.call("sub_mean", "savfi_sub_mean_f32", x, out, mean, ws, N * C, H * W, nbytes=12 * x.numel())
         return out, mean
 
     @staticmethod
@@ -584,12 +532,9 @@ class _MtUpdate(torch.autograd.Function):
                     dst = list(torch.zeros(len(idx), dtype=torch.float32, device=dev).unbind(0))
                 else:
                     dst = [torch.empty_like(go) for go in gos]
-                lib = _hip.lib()
                 numel = [ctx.numel[i] for i in idx]
-                args = (ctx.lr_mode, len(idx), _hip.ptr_array(gos), _hip.ptr_array(dirs), _hip.ptr_array(dst),
-                        _hip.i64_array(numel), ctx.dir_scale, _hip.current_stream())
-                _hip.launch("mt_update_bwd", lambda: _hip.check(lib.savfi_mt_update_bwd_f32(*args),
-                                                                 "savfi_mt_update_bwd_f32"))
+                _hip.call("mt_update_bwd", "savfi_mt_update_bwd_f32", ctx.lr_mode, len(idx), _hip.ptr_array(gos), _hip.ptr_array(dirs),
+                          _hip.ptr_array(dst), _hip.i64_array(numel), ctx.dir_scale)
                 for j, i in enumerate(idx):
                     if ctx.lr_mode == _hip.LR_ELEMENT and tuple(ctx.w_shapes[i]) != tuple(ctx.lr_shapes[i]):
                         g_lrs[i] = dst[j].sum(0)         # weights stacked over tasks, ONE element-wise lr table: add the tasks
@@ -616,16 +561,13 @@ def _launch_mt_update(rule, lr_mode, ws, gs, lrs, ms, ss, outs, coefs, bc1, sqrt
         bc1, sqrt_bc2 = rep(bc1), rep(sqrt_bc2)
         ws_, gs, ms, ss, outs, coefs = cut(ws), cut(gs), cut(ms), cut(ss), cut(outs), cut(coefs)
         ws = ws_
-    lib = _hip.lib()
-    args = (rule, lr_mode, len(ws), _hip.ptr_array(ws), _hip.ptr_array(gs), _hip.ptr_array(lrs),
-            _hip.ptr_array(ms) if ms is not None else None, _hip.ptr_array(ss) if ss is not None else None,
-            _hip.ptr_array(outs), _hip.ptr_array(coefs) if coefs is not None else None,
-            _hip.i64_array([w.numel() for w in ws]),
-            _hip.f32_array(bc1) if bc1 is not None else None, _hip.f32_array(sqrt_bc2) if sqrt_bc2 is not None else None,
-            beta1, beta2, eps, _hip.current_stream())
     per_el = 12 + (4 if lr_mode == _hip.LR_ELEMENT else 0) + (8 if ms is not None else 0) + (8 if ss is not None else 0) + (4 if coefs is not None else 0)
-    _hip.launch("mt_update", lambda: _hip.check(lib.savfi_mt_update_f32(*args), "savfi_mt_update_f32"),
-                nbytes=per_el * sum(w.numel() for w in ws))
+    _hip.call("mt_update", "savfi_mt_update_f32", rule, lr_mode, len(ws), _hip.ptr_array(ws), _hip.ptr_array(gs), _hip.ptr_array(lrs),
+              _hip.ptr_array(ms) if ms is not None else None, _hip.ptr_array(ss) if ss is not None else None,
+              _hip.ptr_array(outs), _hip.ptr_array(coefs) if coefs is not None else None,
+              _hip.i64_array([w.numel() for w in ws]),
+              _hip.f32_array(bc1) if bc1 is not None else None, _hip.f32_array(sqrt_bc2) if sqrt_bc2 is not None else None,
+              beta1, beta2, eps, nbytes=per_el * sum(w.numel() for w in ws))
 
 
 def mt_update(rule, lr_mode, weights, grads, lrs, m=None, s=None, bc1=None, sqrt_bc2=None,
@@ -672,10 +614,7 @@ def mt_mean(tensors):
     ts = [t.detach().contiguous() for t in tensors]
     _hip.require_cuda(*ts)
     out = torch.zeros(len(ts), dtype=torch.float32, device=ts[0].device)
-    lib = _hip.lib()
-    args = (len(ts), _hip.ptr_array(ts), _hip.i64_array([t.numel() for t in ts]), out.data_ptr(),
-            _hip.current_stream())
-    _hip.launch("mt_mean", lambda: _hip.check(lib.savfi_mt_mean_f32(*args), "savfi_mt_mean_f32"))
+    _hip.call("mt_mean", "savfi_mt_mean_f32", len(ts), _hip.ptr_array(ts), _hip.i64_array([t.numel() for t in ts]), out)
     return out
 
 
@@ -685,11 +624,8 @@ class _MtScale(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         _hip.require_cuda(gamma, *ws)
         outs = [torch.empty_like(w) for w in ws]
-        lib = _hip.lib()
-        numel = [w.numel() for w in ws]
-        args = (len(ws), _hip.ptr_array(ws), gamma.data_ptr(), _hip.ptr_array(outs), _hip.i64_array(numel),
-                _hip.current_stream())
-        _hip.launch("mt_scale", lambda: _hip.check(lib.savfi_mt_scale_f32(*args), "savfi_mt_scale_f32"))
+        _hip.call("mt_scale", "savfi_mt_scale_f32", len(ws), _hip.ptr_array(ws), gamma, _hip.ptr_array(outs),
+                  _hip.i64_array([w.numel() for w in ws]))
         ctx.save_for_backward(gamma, *ws)
         return tuple(outs)
 
@@ -709,12 +645,8 @@ class _MtScale(torch.autograd.Function):
             full = len(live) == n
             gam_l = gamma if full else gamma[live].contiguous()
             gg_l = None if g_gamma is None else (g_gamma if full else torch.zeros_like(gam_l))
-            lib = _hip.lib()
-            args = (len(live), _hip.ptr_array(gos), _hip.ptr_array(wl), gam_l.data_ptr(), _hip.ptr_array(gw_l),
-                    None if gg_l is None else gg_l.data_ptr(), _hip.i64_array([w.numel() for w in wl]),
-                    _hip.current_stream())
-            _hip.launch("mt_scale_bwd", lambda: _hip.check(lib.savfi_mt_scale_bwd_f32(*args),
-                                                            "savfi_mt_scale_bwd_f32"))
+            _hip.call("mt_scale_bwd", "savfi_mt_scale_bwd_f32", len(live), _hip.ptr_array(gos), _hip.ptr_array(wl), gam_l,
+                      _hip.ptr_array(gw_l), gg_l, _hip.i64_array([w.numel() for w in wl]))
             for j, i in enumerate(live):
                 g_ws[i] = gw_l[j]
             if g_gamma is not None and not full:
@@ -731,10 +663,8 @@ def mt_scale_grads(gamma, weights, g_outs):
     _hip.require_cuda(gamma, *ws, *gos)
     gws = [torch.empty_like(w) for w in ws]
     gg = torch.zeros_like(gamma)
-    lib = _hip.lib()
-    args = (len(ws), _hip.ptr_array(gos), _hip.ptr_array(ws), gamma.data_ptr(), _hip.ptr_array(gws), gg.data_ptr(),
-            _hip.i64_array([w.numel() for w in ws]), _hip.current_stream())
-    _hip.launch("mt_scale_bwd", lambda: _hip.check(lib.savfi_mt_scale_bwd_f32(*args), "savfi_mt_scale_bwd_f32"))
+    _hip.call("mt_scale_bwd", "savfi_mt_scale_bwd_f32", len(ws), _hip.ptr_array(gos), _hip.ptr_array(ws), gamma, _hip.ptr_array(gws), gg,
+              _hip.i64_array([w.numel() for w in ws]))
     return gg, gws
 
 
@@ -765,10 +695,7 @@ def mt_scale_into(gamma, weights, outs):
     gamma = gamma.detach().contiguous()
     _hip.require_cuda(gamma, *ws, *outs)
     assert len(ws) == len(outs) and all(o.is_contiguous() and o.numel() == w.numel() and o.dtype == w.dtype for o, w in zip(outs, ws))
-    lib = _hip.lib()
-    args = (len(ws), _hip.ptr_array(ws), gamma.data_ptr(), _hip.ptr_array(outs), _hip.i64_array([w.numel() for w in ws]),
-            _hip.current_stream())
-    _hip.launch("mt_scale", lambda: _hip.check(lib.savfi_mt_scale_f32(*args), "savfi_mt_scale_f32"))
+    _hip.call("mt_scale", "savfi_mt_scale_f32", len(ws), _hip.ptr_array(ws), gamma, _hip.ptr_array(outs), _hip.i64_array([w.numel() for w in ws]))
 
 
 def mt_copy(dsts, srcs):
@@ -812,10 +739,7 @@ class MtCopy:
                 mt_copy([d.detach() for d in self.dsts], [s.detach() for s in self.srcs])
             return
         n, pw, _, po, numel = self.args
-        gamma = _ones(n, self.dsts[0].device)
-        lib = _hip.lib()
-        _hip.launch("mt_scale", lambda: _hip.check(lib.savfi_mt_scale_f32(n, pw, gamma.data_ptr(), po, numel, _hip.current_stream()),
-                                                   "savfi_mt_scale_f32"))
+        _hip.call("mt_scale", "savfi_mt_scale_f32", n, pw, _ones(n, self.dsts[0].device), po, numel)
 
 
 def mt_clone(srcs):
@@ -829,21 +753,24 @@ def mt_clone(srcs):
 # --------------------------------------------------------------------------------------------
 # Fused L1 / MSE                                                     (loss.py:287-290)
 # --------------------------------------------------------------------------------------------
+def _row_means_buffers(a, b):
+    """(rows, n, result [rows], scratch) of a per-row mean over a, b [rows, ...] (_L1Mse, _Charbonnier: one scratch rule)."""
+    _hip.require_cuda(a, b)
+    assert a.shape == b.shape
+    rows = a.shape[0]
+    n = a.numel() // rows
+    res = torch.empty(rows, dtype=torch.float32, device=a.device)
+    scratch = torch.empty(_workspace_floats("savfi_l1_mse_scratch_floats", rows, n), dtype=torch.float32, device=a.device)
+    return rows, n, res, scratch
+
+
 class _L1Mse(torch.autograd.Function):
     """a, b [rows, ...] -> float32[rows] of per-row mean |a-b| (kind 0) / mean (a-b)^2 (kind 1); deterministic."""
 
     @staticmethod
     def forward(ctx, kind, a, b):
-        _hip.require_cuda(a, b)
-        assert a.shape == b.shape
-        rows = a.shape[0]
-        n = a.numel() // rows
-        res = torch.empty(rows, dtype=torch.float32, device=a.device)
-        scratch = torch.empty(_workspace_floats("savfi_l1_mse_scratch_floats", rows, n), dtype=torch.float32, device=a.device)
-        lib = _hip.lib()
-        _hip.launch("l1_mse", lambda: _hip.check(lib.savfi_l1_mse_f32(
-            kind, a.data_ptr(), b.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, n, _hip.current_stream()),
-            "savfi_l1_mse_f32"))
+        rows, n, res, scratch = _row_means_buffers(a, b)
+        _hip.call("l1_mse", "savfi_l1_mse_f32", kind, a, b, res, scratch, rows, n)
         ctx.kind = kind
         ctx.save_for_backward(a, b)
         return res
@@ -855,10 +782,7 @@ class _L1Mse(torch.autograd.Function):
         g = g.contiguous()
         ga = torch.empty_like(a)
         rows = a.shape[0]
-        lib = _hip.lib()
-        _hip.launch("l1_mse_bwd", lambda: _hip.check(lib.savfi_l1_mse_bwd_f32(
-            ctx.kind, a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), rows, a.numel() // rows,
-            _hip.current_stream()), "savfi_l1_mse_bwd_f32"))
+        _hip.call("l1_mse_bwd", "savfi_l1_mse_bwd_f32", ctx.kind, a, b, g, ga, rows, a.numel() // rows)
         gb = -ga if ctx.needs_input_grad[2] else None
         return None, ga, gb
 
@@ -913,10 +837,7 @@ class _SsimLoss(torch.autograd.Function):
         res = torch.empty(out_rows, dtype=torch.float32, device=sr.device)
         word = torch.empty(out_rows, dtype=torch.int32, device=sr.device)
         scratch = torch.empty(_workspace_floats("savfi_ssim_scratch_floats", N, C, H, W), dtype=torch.float32, device=sr.device)
-        lib = _hip.lib()
-        _hip.launch("ssim_loss", lambda: _hip.check(lib.savfi_ssim_loss_f32(
-            sr.data_ptr(), hr.data_ptr(), res.data_ptr(), word.data_ptr(), scratch.data_ptr(), N, C, H, W, mode,
-            _hip.current_stream()), "savfi_ssim_loss_f32"), nbytes=8 * sr.numel())
+        _hip.call("ssim_loss", "savfi_ssim_loss_f32", sr, hr, res, word, scratch, N, C, H, W, mode, nbytes=8 * sr.numel())
         ctx.batch = mode == _hip.SSIM_RANGE_BATCH
         ctx.save_for_backward(sr, hr, word)
         return res
@@ -929,38 +850,47 @@ class _SsimLoss(torch.autograd.Function):
         rows, ch = (1, N * C) if ctx.batch else (N, C)      # one loss over the batch: the samples are further channel planes
         g = g.contiguous()
         gsr = torch.empty_like(sr)
-        lib = _hip.lib()
-        _hip.launch("ssim_loss_bwd", lambda: _hip.check(lib.savfi_ssim_loss_bwd_f32(
-            sr.data_ptr(), hr.data_ptr(), g.data_ptr(), word.data_ptr(), gsr.data_ptr(), rows, ch, H, W,
-            _hip.current_stream()), "savfi_ssim_loss_bwd_f32"), nbytes=12 * sr.numel())
+        _hip.call("ssim_loss_bwd", "savfi_ssim_loss_bwd_f32", sr, hr, g, word, gsr, rows, ch, H, W, nbytes=12 * sr.numel())
         return gsr, None, None
 
 
 @functools.lru_cache(maxsize=None)
-def _ssim_taps(device):
-    """The 11 fp32 window taps of pytorch_msssim.create_window on `device` (built once per device)."""
+def _gauss_taps(n, device):
+    """The n fp32 taps of pytorch_msssim.gaussian(n, 1.5) on `device` (built once per size and device); n = 11: create_window's."""
     import math
-    g = torch.tensor([math.exp(-(x - 5) ** 2 / 4.5) for x in range(11)], dtype=torch.float32)
+    g = torch.tensor([math.exp(-(x - n // 2) ** 2 / 4.5) for x in range(n)], dtype=torch.float32)
     return (g / g.sum()).to(device)
 
 
-def _ssim_composed(sr, hr, per_sample):
-    """The same formula from differentiable device ops (what --second_order takes): separable 11-tap window, the range decided
-    by torch.where on device tensors (no host read)."""
-    C = sr.shape[1]
-    taps = _ssim_taps(sr.device)
-    wr, wc = taps.view(1, 1, 1, 11).expand(C, 1, 1, 11), taps.view(1, 1, 11, 1).expand(C, 1, 11, 1)
+def _ssim_level(img1, img2, extremes, fixed_cls=None):
+    """One level of the composed SSIM / MS-SSIM from differentiable device ops -> (SSIM map, v1, v2) with v1 / v2 the contrast map
+    (divided by the caller that wants it): the separable window of min(11, H, W) taps, the dynamic range by the reference's rule from
+    `extremes` = (max, min) of the detached first image as device tensors (torch.where: no host read; the caller reduces them, whole
+    batch or per sample) or the fixed class `fixed_cls`, the five windowed moments."""
+    C = img1.shape[1]
+    n = min(11, img1.shape[2], img1.shape[3])
+    taps = _gauss_taps(n, img1.device)
+    wr, wc = taps.view(1, 1, 1, n).expand(C, 1, 1, n), taps.view(1, 1, n, 1).expand(C, 1, n, 1)
 
     def win(x):
         return torch.nn.functional.conv2d(torch.nn.functional.conv2d(x, wr, groups=C), wc, groups=C)
-    d = sr.detach()
-    hi, lo = (d.amax((1, 2, 3), keepdim=True), d.amin((1, 2, 3), keepdim=True)) if per_sample else (d.max(), d.min())
-    one = torch.ones_like(hi)
-    L = torch.where(hi > 128, 255 * one, one) + torch.where(lo < -0.5, one, 0 * one)
+    if fixed_cls is None:
+        hi, lo = extremes
+        one = torch.ones_like(hi)
+        L = torch.where(hi > 128, 255 * one, one) + torch.where(lo < -0.5, one, 0 * one)
+    else:
+        L = (1.0, 2.0, 255.0, 256.0)[fixed_cls]
     C1, C2 = (0.01 * L) ** 2, (0.03 * L) ** 2
-    mu1, mu2 = win(sr), win(hr)
-    s1, s2, s12 = win(sr * sr) - mu1 * mu1, win(hr * hr) - mu2 * mu2, win(sr * hr) - mu1 * mu2
-    smap = ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2))
+    mu1, mu2 = win(img1), win(img2)
+    s1, s2, s12 = win(img1 * img1) - mu1 * mu1, win(img2 * img2) - mu2 * mu2, win(img1 * img2) - mu1 * mu2
+    v1, v2 = 2 * s12 + C2, s1 + s2 + C2
+    return ((2 * mu1 * mu2 + C1) * v1) / ((mu1 * mu1 + mu2 * mu2 + C1) * v2), v1, v2
+
+
+def _ssim_composed(sr, hr, per_sample):
+    """The same formula from differentiable device ops (what --second_order takes): one _ssim_level with the 11-tap window."""
+    d = sr.detach()
+    smap, _, _ = _ssim_level(sr, hr, (d.amax((1, 2, 3), keepdim=True), d.amin((1, 2, 3), keepdim=True)) if per_sample else (d.max(), d.min()))
     return (1 - (smap.flatten(1).mean(1) if per_sample else smap.mean())) / 2
 
 
@@ -1007,10 +937,7 @@ def psnr_ssim(pred01, tgt01, want_sq_sum=False):
     res = torch.empty((rows, 2), dtype=torch.float32, device=pred01.device)
     sq = torch.empty(rows, dtype=torch.int64, device=pred01.device) if want_sq_sum else None
     scratch = torch.empty(_workspace_floats("savfi_psnr_ssim_scratch_bytes", rows, C, H, W), dtype=torch.uint8, device=pred01.device)
-    lib = _hip.lib()
-    _hip.launch("psnr_ssim", lambda: _hip.check(lib.savfi_psnr_ssim_f32(
-        pred01.data_ptr(), tgt01.data_ptr(), res.data_ptr(), _ptr(sq), scratch.data_ptr(), rows, C, H, W, _hip.current_stream()),
-        "savfi_psnr_ssim_f32"), nbytes=8 * pred01.numel())
+    _hip.call("psnr_ssim", "savfi_psnr_ssim_f32", pred01, tgt01, res, sq, scratch, rows, C, H, W, nbytes=8 * pred01.numel())
     return (res[:, 0], res[:, 1]) + ((sq,) if want_sq_sum else ())
 
 
@@ -1021,21 +948,20 @@ _MSSSIM_LEVELS = 5
 _MSSSIM_VAL_RANGES = {1: 0, 2: 1, 255: 2, 256: 3}
 
 
-def _msssim_dims(img1, fold):
-    """The call's (rows, C, H, W); fold: one value over the batch under a FIXED class -- the samples are further channel planes of one row."""
-    N, C, H, W = img1.shape
+def _fold_dims(img, fold):
+    """The (rows, C, H, W) a loss kernel is called with; fold: one value over the batch (MS-SSIM: under a FIXED class) -- the samples
+    are further channel planes of one row."""
+    N, C, H, W = img.shape
     return (1, N * C, H, W) if fold else (N, C, H, W)
 
 
 def _msssim_launch(img1, img2, mode, normalize, quantize=False, fold=False):
     """-> (result [rows], scratch): the forward launches of savfi_msssim_f32; `scratch` is what the backward needs."""
-    N, C, H, W = _msssim_dims(img1, fold)
+    N, C, H, W = _fold_dims(img1, fold)
     res = torch.empty(1 if mode == _hip.SSIM_RANGE_BATCH else N, dtype=torch.float32, device=img1.device)
     scratch = torch.empty(_workspace_floats("savfi_msssim_scratch_bytes", N, C, H, W) // 4, dtype=torch.float32, device=img1.device)
-    lib = _hip.lib()
-    _hip.launch("msssim", lambda: _hip.check(lib.savfi_msssim_f32(
-        img1.data_ptr(), img2.data_ptr(), res.data_ptr(), scratch.data_ptr(), N, C, H, W, mode, int(bool(normalize)), int(bool(quantize)),
-        _hip.current_stream()), "savfi_msssim_f32"), nbytes=int(8 * img1.numel() * 1.6))
+    _hip.call("msssim", "savfi_msssim_f32", img1, img2, res, scratch, N, C, H, W, mode, int(bool(normalize)), int(bool(quantize)),
+              nbytes=int(8 * img1.numel() * 1.6))
     return res, scratch
 
 
@@ -1058,50 +984,23 @@ class _MsSsim(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         img1, img2 = ctx.saved_tensors
-        N, C, H, W = _msssim_dims(img1, ctx.fold)
+        N, C, H, W = _fold_dims(img1, ctx.fold)
         g = g.contiguous()
         g1 = torch.empty_like(img1)
-        scratch = ctx.scratch
-        lib = _hip.lib()
-        _hip.launch("msssim_bwd", lambda: _hip.check(lib.savfi_msssim_bwd_f32(
-            img1.data_ptr(), img2.data_ptr(), g.data_ptr(), scratch.data_ptr(), g1.data_ptr(), N, C, H, W, ctx.mode,
-            _hip.current_stream()), "savfi_msssim_bwd_f32"), nbytes=int(12 * img1.numel() * 1.6))
+        _hip.call("msssim_bwd", "savfi_msssim_bwd_f32", img1, img2, g, ctx.scratch, g1, N, C, H, W, ctx.mode,
+                  nbytes=int(12 * img1.numel() * 1.6))
         return g1, None, None, None, None
 
 
-@functools.lru_cache(maxsize=None)
-def _msssim_taps(n, device):
-    """The n fp32 taps of pytorch_msssim.gaussian(n, 1.5) on `device`."""
-    import math
-    g = torch.tensor([math.exp(-(x - n // 2) ** 2 / 4.5) for x in range(n)], dtype=torch.float32)
-    return (g / g.sum()).to(device)
-
-
 def _msssim_composed(img1, img2, per_sample, fixed_cls, normalize):
-    """The same value from differentiable device ops (what --second_order takes): separable windows, the range of every level decided
-    by torch.where on device tensors (no host read), avg_pool2d between the levels."""
-    C = img1.shape[1]
+    """The same value from differentiable device ops (what --second_order takes): one _ssim_level per level, its range decided from
+    that level's image, avg_pool2d between the levels."""
     dims = (1, 2, 3) if per_sample else (0, 1, 2, 3)
     ms, mc = [], []
     for _ in range(_MSSSIM_LEVELS):
-        n = min(11, img1.shape[2], img1.shape[3])
-        taps = _msssim_taps(n, img1.device)
-        wr, wc = taps.view(1, 1, 1, n).expand(C, 1, 1, n), taps.view(1, 1, n, 1).expand(C, 1, n, 1)
-
-        def win(x):
-            return torch.nn.functional.conv2d(torch.nn.functional.conv2d(x, wr, groups=C), wc, groups=C)
-        if fixed_cls is None:
-            d = img1.detach()
-            hi, lo = d.amax(dims, keepdim=True), d.amin(dims, keepdim=True)
-            one = torch.ones_like(hi)
-            L = torch.where(hi > 128, 255 * one, one) + torch.where(lo < -0.5, one, 0 * one)
-        else:
-            L = (1.0, 2.0, 255.0, 256.0)[fixed_cls]
-        C1, C2 = (0.01 * L) ** 2, (0.03 * L) ** 2
-        mu1, mu2 = win(img1), win(img2)
-        s1, s2, s12 = win(img1 * img1) - mu1 * mu1, win(img2 * img2) - mu2 * mu2, win(img1 * img2) - mu1 * mu2
-        v1, v2 = 2 * s12 + C2, s1 + s2 + C2
-        smap = ((2 * mu1 * mu2 + C1) * v1) / ((mu1 * mu1 + mu2 * mu2 + C1) * v2)
+        d = img1.detach()
+        extremes = (d.amax(dims, keepdim=True), d.amin(dims, keepdim=True)) if fixed_cls is None else None
+        smap, v1, v2 = _ssim_level(img1, img2, extremes, fixed_cls)
         ms.append(smap.mean(dims))
         mc.append((v1 / v2).mean(dims))
         img1, img2 = torch.nn.functional.avg_pool2d(img1, (2, 2)), torch.nn.functional.avg_pool2d(img2, (2, 2))
@@ -1157,12 +1056,6 @@ def msssim_metric(pred01, tgt01):
 LAP_LEVELS = 5
 
 
-def _lap_dims(sr, fold):
-    """The call's (rows, C, H, W); fold: one value over the batch -- the samples are further channel planes of one row."""
-    N, C, H, W = sr.shape
-    return (1, N * C, H, W) if fold else (N, C, H, W)
-
-
 class _LapLoss(torch.autograd.Function):
     """sr, hr [N,C,H,W] -> float32[N] (every sample on its own) or float32[1] (fold: one value over the batch); capturable; deterministic."""
 
@@ -1171,14 +1064,11 @@ class _LapLoss(torch.autograd.Function):
         _hip.require_cuda(sr, hr)
         if ctx.needs_input_grad[1]:
             raise NotImplementedError("lap_loss differentiates w.r.t. the prediction only")
-        rows, C, H, W = _lap_dims(sr, fold)
+        rows, C, H, W = _fold_dims(sr, fold)
         res = torch.empty(rows, dtype=torch.float32, device=sr.device)
         scratch = torch.empty(_workspace_floats("savfi_laploss_scratch_bytes", rows, C, H, W, levels) // 4, dtype=torch.float32,
                               device=sr.device)
-        lib = _hip.lib()
-        _hip.launch("laploss", lambda: _hip.check(lib.savfi_laploss_f32(
-            sr.data_ptr(), hr.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, C, H, W, levels, _hip.current_stream()),
-            "savfi_laploss_f32"), nbytes=int(4 * sr.numel() * (2 + 2 / 3)))
+        _hip.call("laploss", "savfi_laploss_f32", sr, hr, res, scratch, rows, C, H, W, levels, nbytes=int(4 * sr.numel() * (2 + 2 / 3)))
         ctx.levels, ctx.fold = levels, fold
         ctx.scratch = scratch      # the pyramid of the difference, and the backward's work area: not a saved tensor (the backward writes into it)
         ctx.save_for_backward(sr, hr)
@@ -1188,14 +1078,11 @@ class _LapLoss(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         sr, hr = ctx.saved_tensors
-        rows, C, H, W = _lap_dims(sr, ctx.fold)
+        rows, C, H, W = _fold_dims(sr, ctx.fold)
         g = g.contiguous()
         gsr = torch.empty_like(sr)
-        scratch = ctx.scratch
-        lib = _hip.lib()
-        _hip.launch("laploss_bwd", lambda: _hip.check(lib.savfi_laploss_bwd_f32(
-            sr.data_ptr(), hr.data_ptr(), g.data_ptr(), scratch.data_ptr(), gsr.data_ptr(), rows, C, H, W, ctx.levels,
-            _hip.current_stream()), "savfi_laploss_bwd_f32"), nbytes=int(4 * sr.numel() * (4 + 1 / 3)))
+        _hip.call("laploss_bwd", "savfi_laploss_bwd_f32", sr, hr, g, ctx.scratch, gsr, rows, C, H, W, ctx.levels,
+                  nbytes=int(4 * sr.numel() * (4 + 1 / 3)))
         return gsr, None, None, None
 
 
@@ -1272,10 +1159,7 @@ class _CensusLoss(torch.autograd.Function):
         rows, n = (1, N) if fold else (N, 1)
         res = torch.empty(rows, dtype=torch.float32, device=sr.device)
         scratch = torch.empty(_workspace_floats("savfi_census_scratch_bytes", rows, n, C, H, W) // 8, dtype=torch.float64, device=sr.device)
-        lib = _hip.lib()
-        _hip.launch("census", lambda: _hip.check(lib.savfi_census_f32(
-            sr.data_ptr(), hr.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, n, C, H, W, _hip.current_stream()),
-            "savfi_census_f32"), nbytes=8 * sr.numel())
+        _hip.call("census", "savfi_census_f32", sr, hr, res, scratch, rows, n, C, H, W, nbytes=8 * sr.numel())
         ctx.fold = fold
         ctx.save_for_backward(sr, hr)
         return res
@@ -1288,10 +1172,7 @@ class _CensusLoss(torch.autograd.Function):
         rows, n = (1, N) if ctx.fold else (N, 1)
         g = g.contiguous()
         gsr = torch.empty_like(sr)
-        lib = _hip.lib()
-        _hip.launch("census_bwd", lambda: _hip.check(lib.savfi_census_bwd_f32(
-            sr.data_ptr(), hr.data_ptr(), g.data_ptr(), gsr.data_ptr(), rows, n, C, H, W, _hip.current_stream()),
-            "savfi_census_bwd_f32"), nbytes=12 * sr.numel())
+        _hip.call("census_bwd", "savfi_census_bwd_f32", sr, hr, g, gsr, rows, n, C, H, W, nbytes=12 * sr.numel())
         return gsr, None, None
 
 
@@ -1357,9 +1238,7 @@ def frames_to_u8(x):
         raise ValueError("frames_to_u8 writes 1 or 3 channels, got %d" % C)
     out = torch.empty((N, H, W, C), dtype=torch.uint8, device=x.device)
     if out.numel():
-        lib = _hip.lib()
-        _hip.launch("frames_to_u8", lambda: _hip.check(lib.savfi_frames_f32_to_u8(
-            x4.data_ptr(), out.data_ptr(), N, C, H, W, _hip.current_stream()), "savfi_frames_f32_to_u8"), nbytes=5 * x4.numel())
+        _hip.call("frames_to_u8", "savfi_frames_f32_to_u8", x4, out, N, C, H, W, nbytes=5 * x4.numel())
     return out if x.dim() == 4 else out[0] if x.dim() == 3 else out[0, :, :, 0]
 
 
@@ -1390,10 +1269,8 @@ class _FilterInterpolation(torch.autograd.Function):
             raise ValueError("filter_interpolation needs input [B,C,H,W], flow [B,2,H,W] and a 4 x 4 filter [B,16,H,W], got %s, %s, %s"
                              % (tuple(input1.shape), tuple(input2.shape), tuple(input3.shape)))
         out = torch.empty_like(input1)
-        lib = _hip.lib()
-        _hip.launch("filterinterp_fwd", lambda: _hip.check(lib.savfi_filterinterp_fwd_f32(
-            input1.data_ptr(), input2.data_ptr(), input3.data_ptr(), out.data_ptr(), B, C, H, W, 4, _hip.current_stream()),
-            "savfi_filterinterp_fwd_f32"), nbytes=filterinterp_bytes(B, C, H, W))
+        _hip.call("filterinterp_fwd", "savfi_filterinterp_fwd_f32", input1, input2, input3, out, B, C, H, W, 4,
+                  nbytes=filterinterp_bytes(B, C, H, W))
         ctx.save_for_backward(input1, input2, input3)
         return out
 
@@ -1408,10 +1285,8 @@ class _FilterInterpolation(torch.autograd.Function):
         g1 = torch.empty_like(input1) if need[0] else None
         g2 = torch.empty_like(input2) if need[1] else None
         g3 = torch.empty_like(input3) if need[2] else None
-        lib = _hip.lib()
-        _hip.launch("filterinterp_bwd", lambda: _hip.check(lib.savfi_filterinterp_bwd_f32(
-            input1.data_ptr(), input2.data_ptr(), input3.data_ptr(), gradoutput.data_ptr(), _ptr(g1), _ptr(g2), _ptr(g3), B, C, H, W, 4,
-            _hip.current_stream()), "savfi_filterinterp_bwd_f32"), nbytes=filterinterp_bytes(B, C, H, W, grads=1))
+        _hip.call("filterinterp_bwd", "savfi_filterinterp_bwd_f32", input1, input2, input3, gradoutput, g1, g2, g3, B, C, H, W, 4,
+                  nbytes=filterinterp_bytes(B, C, H, W, grads=1))
         return g1, g2, g3
 
 
@@ -1434,10 +1309,8 @@ def filter_interpolation_into(out, c_off, input, flow, filt):
     if flow.shape != (B, 2, H, W) or filt.shape != (B, 16, H, W) or out.dim() != 4 or (out.shape[0], out.shape[2], out.shape[3]) != (B, H, W):
         raise ValueError("filter_interpolation_into needs input [B,C,H,W], flow [B,2,H,W], a 4 x 4 filter [B,16,H,W] and out "
                          "[B,C_total,H,W], got %s, %s, %s, %s" % (tuple(input.shape), tuple(flow.shape), tuple(filt.shape), tuple(out.shape)))
-    lib = _hip.lib()
-    _hip.launch("filterinterp_fwd_slice", lambda: _hip.check(lib.savfi_filterinterp_fwd_slice_f32(
-        input.data_ptr(), flow.data_ptr(), filt.data_ptr(), out.data_ptr(), B, C, H, W, 4, out.shape[1], int(c_off),
-        _hip.current_stream()), "savfi_filterinterp_fwd_slice_f32"), nbytes=filterinterp_bytes(B, C, H, W))
+    _hip.call("filterinterp_fwd_slice", "savfi_filterinterp_fwd_slice_f32", input, flow, filt, out, B, C, H, W, 4, out.shape[1], int(c_off),
+              nbytes=filterinterp_bytes(B, C, H, W))
     return out
 
 
@@ -1452,10 +1325,8 @@ class _DepthFlowProjection(torch.autograd.Function):
         count = torch.empty((B, 1, H, W), dtype=input1.dtype, device=input1.device)
         output = torch.empty_like(input1)
         scratch = torch.empty(_workspace_floats("savfi_depthflowproj_scratch_bytes", B, H, W), dtype=torch.uint8, device=input1.device)
-        lib = _hip.lib()
-        _hip.launch("depthflowproj_fwd", lambda: _hip.check(lib.savfi_depthflowproj_fwd_f32(
-            input1.data_ptr(), input2.data_ptr(), count.data_ptr(), output.data_ptr(), scratch.data_ptr(), B, H, W, int(bool(fillhole)),
-            _hip.current_stream()), "savfi_depthflowproj_fwd_f32"), nbytes=depthflowproj_bytes(B, H, W))
+        _hip.call("depthflowproj_fwd", "savfi_depthflowproj_fwd_f32", input1, input2, count, output, scratch, B, H, W, int(bool(fillhole)),
+                  nbytes=depthflowproj_bytes(B, H, W))
         # as the reference saves them (DepthFlowProjectionLayer.py:47): the output AFTER the hole fill
         ctx.save_for_backward(input1, input2, count, output)
         ctx.mark_non_differentiable(count)
@@ -1470,10 +1341,8 @@ class _DepthFlowProjection(torch.autograd.Function):
         need = ctx.needs_input_grad
         g1 = torch.empty_like(input1) if need[0] else None       # a gradient that is not needed goes to the C ABI as NULL
         g2 = torch.empty_like(input2) if need[1] else None
-        lib = _hip.lib()
-        _hip.launch("depthflowproj_bwd", lambda: _hip.check(lib.savfi_depthflowproj_bwd_f32(
-            input1.data_ptr(), input2.data_ptr(), count.data_ptr(), output.data_ptr(), gradoutput.data_ptr(), _ptr(g1), _ptr(g2),
-            B, H, W, _hip.current_stream()), "savfi_depthflowproj_bwd_f32"), nbytes=depthflowproj_bytes(B, H, W, grads=1))
+        _hip.call("depthflowproj_bwd", "savfi_depthflowproj_bwd_f32", input1, input2, count, output, gradoutput, g1, g2, B, H, W,
+                  nbytes=depthflowproj_bytes(B, H, W, grads=1))
         return g1, g2, None
 
 
@@ -1509,10 +1378,7 @@ class _Correlation(torch.autograd.Function):
         if f2.shape != f1.shape:
             raise ValueError("correlation needs two feature maps of one shape [N,C,H,W], got %s, %s" % (tuple(f1.shape), tuple(f2.shape)))
         out = torch.empty((N, (2 * md + 1) ** 2, H, W), dtype=f1.dtype, device=f1.device)       # written completely by the kernel
-        lib = _hip.lib()
-        _hip.launch("correlation_fwd", lambda: _hip.check(lib.savfi_correlation_fwd_f32(
-            f1.data_ptr(), f2.data_ptr(), out.data_ptr(), N, C, H, W, md, slope, _hip.current_stream()),
-            "savfi_correlation_fwd_f32"), nbytes=correlation_bytes(N, C, H, W, md))
+        _hip.call("correlation_fwd", "savfi_correlation_fwd_f32", f1, f2, out, N, C, H, W, md, slope, nbytes=correlation_bytes(N, C, H, W, md))
         ctx.md, ctx.slope = md, slope
         ctx.save_for_backward(f1, f2, out if slope != 1.0 else None)
         return out
@@ -1526,10 +1392,8 @@ class _Correlation(torch.autograd.Function):
         need = ctx.needs_input_grad
         g1 = torch.empty_like(f1) if need[0] else None          # a gradient that is not needed goes to the C ABI as NULL
         g2 = torch.empty_like(f2) if need[1] else None
-        lib = _hip.lib()
-        _hip.launch("correlation_bwd", lambda: _hip.check(lib.savfi_correlation_bwd_f32(
-            f1.data_ptr(), f2.data_ptr(), gout.data_ptr(), _ptr(out), ctx.slope, _ptr(g1), _ptr(g2), N, C, H, W, ctx.md,
-            _hip.current_stream()), "savfi_correlation_bwd_f32"), nbytes=correlation_bytes(N, C, H, W, ctx.md, grads=1))
+        _hip.call("correlation_bwd", "savfi_correlation_bwd_f32", f1, f2, gout, out, ctx.slope, g1, g2, N, C, H, W, ctx.md,
+                  nbytes=correlation_bytes(N, C, H, W, ctx.md, grads=1))
         return g1, g2, None, None
 
 
@@ -1553,10 +1417,7 @@ def pwc_warp(img, flow, scale=1.0):
     if flow.shape != (N, 2, H, W):
         raise ValueError("pwc_warp needs img [N,C,H,W] and flow [N,2,H,W], got %s, %s" % (tuple(img.shape), tuple(flow.shape)))
     out = torch.empty_like(img)
-    lib = _hip.lib()
-    _hip.launch("pwcwarp_fwd", lambda: _hip.check(lib.savfi_pwcwarp_fwd_f32(
-        img.data_ptr(), flow.data_ptr(), float(scale), out.data_ptr(), N, C, H, W, _hip.current_stream()),
-        "savfi_pwcwarp_fwd_f32"), nbytes=pwc_warp_bytes(N, C, H, W))
+    _hip.call("pwcwarp_fwd", "savfi_pwcwarp_fwd_f32", img, flow, float(scale), out, N, C, H, W, nbytes=pwc_warp_bytes(N, C, H, W))
     return out
 
 
@@ -1604,10 +1465,7 @@ def bn_stats(x, n_per_group, mean=None, var=None):
         raise ValueError("mean and var must be [%d, %d] views with one group stride" % (G, C))
     nscratch = _workspace_floats("savfi_bn_stats_scratch_floats", N, C, H, W, n_per_group)
     scratch = x.new_empty(nscratch) if nscratch else None
-    lib = _hip.lib()
-    _hip.launch("bn_stats", lambda: _hip.check(lib.savfi_bn_stats_f32(
-        x.data_ptr(), mean.data_ptr(), var.data_ptr(), sm, None if scratch is None else scratch.data_ptr(), N, C, H, W, n_per_group,
-        _hip.current_stream()), "savfi_bn_stats_f32"), nbytes=8 * x.numel())
+    _hip.call("bn_stats", "savfi_bn_stats_f32", x, mean, var, sm, scratch, N, C, H, W, n_per_group, nbytes=8 * x.numel())
     return mean, var
 
 
@@ -1630,11 +1488,8 @@ def bn_apply_relu(x, mean, var, n_per_group, gamma=None, beta=None, eps=1e-5, ou
         out = x.new_empty(N, C, H, W)
     if out.dim() != 4 or out.shape[0] != N or tuple(out.shape[2:]) != (H, W) or c_off < 0 or c_off + C > out.shape[1]:
         raise ValueError("out %s cannot take channels [%d, %d) of %s" % (tuple(out.shape), c_off, c_off + C, tuple(x.shape)))
-    lib = _hip.lib()
-    _hip.launch("bn_apply_relu", lambda: _hip.check(lib.savfi_bn_apply_relu_f32(
-        x.data_ptr(), mean.data_ptr(), var.data_ptr(), sm, None if gamma is None else gamma.data_ptr(),
-        None if beta is None else beta.data_ptr(), float(eps), out.data_ptr(), N, C, H, W, n_per_group, int(c_off), out.shape[1],
-        _hip.current_stream()), "savfi_bn_apply_relu_f32"), nbytes=8 * x.numel())
+    _hip.call("bn_apply_relu", "savfi_bn_apply_relu_f32", x, mean, var, sm, gamma, beta, float(eps), out, N, C, H, W, n_per_group,
+              int(c_off), out.shape[1], nbytes=8 * x.numel())
     return out
 
 
@@ -1648,10 +1503,8 @@ def bn_running_update(running, stats, unbias, momentum=0.1):
         if not (r.is_cuda and s.is_cuda):
             raise NotImplementedError("savfi HIP ops need device tensors (bn_running_update)")
         assert r.dtype == s.dtype == torch.float32 and r.is_contiguous() and s.is_contiguous() and r.numel() == s.numel()
-    lib = _hip.lib()
-    args = (len(running), _hip.ptr_array(running), _hip.ptr_array(stats), _hip.i64_array([r.numel() for r in running]),
-            _hip.f32_array([float(u) for u in unbias]), float(momentum), _hip.current_stream())
-    _hip.launch("bn_running_update", lambda: _hip.check(lib.savfi_bn_running_update_f32(*args), "savfi_bn_running_update_f32"))
+    _hip.call("bn_running_update", "savfi_bn_running_update_f32", len(running), _hip.ptr_array(running), _hip.ptr_array(stats),
+              _hip.i64_array([r.numel() for r in running]), _hip.f32_array([float(u) for u in unbias]), float(momentum))
 
 
 def max_pool2x2(x):
@@ -1661,9 +1514,7 @@ def max_pool2x2(x):
     _frozen("max_pool2x2", x)
     N, C, H, W = x.shape
     out = x.new_empty(N, C, H // 2, W // 2)
-    lib = _hip.lib()
-    _hip.launch("maxpool2x2", lambda: _hip.check(lib.savfi_maxpool2x2_f32(
-        x.data_ptr(), out.data_ptr(), N * C, H, W, _hip.current_stream()), "savfi_maxpool2x2_f32"), nbytes=5 * out.numel() * 4)
+    _hip.call("maxpool2x2", "savfi_maxpool2x2_f32", x, out, N * C, H, W, nbytes=5 * out.numel() * 4)
     return out
 
 
@@ -1676,10 +1527,7 @@ def upnearest2x_add(low, skip):
     if tuple(skip.shape) != (N, C, 2 * h, 2 * w):
         raise ValueError("skip %s is not exactly twice low %s on both sides" % (tuple(skip.shape), tuple(low.shape)))
     out = torch.empty_like(skip)
-    lib = _hip.lib()
-    _hip.launch("upnearest2x_add", lambda: _hip.check(lib.savfi_upnearest2x_add_f32(
-        low.data_ptr(), skip.data_ptr(), out.data_ptr(), N * C, h, w, 2 * h, 2 * w, _hip.current_stream()),
-        "savfi_upnearest2x_add_f32"), nbytes=9 * low.numel() * 4)
+    _hip.call("upnearest2x_add", "savfi_upnearest2x_add_f32", low, skip, out, N * C, h, w, 2 * h, 2 * w, nbytes=9 * low.numel() * 4)
     return out
 
 
@@ -1691,9 +1539,7 @@ class _AddRelu(torch.autograd.Function):
         _hip.require_cuda(a, r)
         assert a.shape == r.shape
         y = torch.empty_like(a)
-        lib = _hip.lib()
-        _hip.launch("add_relu", lambda: _hip.check(lib.savfi_add_relu_f32(
-            a.data_ptr(), r.data_ptr(), y.data_ptr(), a.numel(), _hip.current_stream()), "savfi_add_relu_f32"), nbytes=12 * a.numel())
+        _hip.call("add_relu", "savfi_add_relu_f32", a, r, y, a.numel(), nbytes=12 * a.numel())
         ctx.save_for_backward(y)
         return y
 
@@ -1718,16 +1564,8 @@ class _Charbonnier(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b, eps):
-        _hip.require_cuda(a, b)
-        assert a.shape == b.shape
-        rows = a.shape[0]
-        n = a.numel() // rows
-        res = torch.empty(rows, dtype=torch.float32, device=a.device)
-        scratch = torch.empty(_workspace_floats("savfi_l1_mse_scratch_floats", rows, n), dtype=torch.float32, device=a.device)
-        lib = _hip.lib()
-        _hip.launch("charbonnier", lambda: _hip.check(lib.savfi_charbonnier_f32(
-            a.data_ptr(), b.data_ptr(), res.data_ptr(), scratch.data_ptr(), rows, n, eps, _hip.current_stream()),
-            "savfi_charbonnier_f32"), nbytes=8 * a.numel())
+        rows, n, res, scratch = _row_means_buffers(a, b)
+        _hip.call("charbonnier", "savfi_charbonnier_f32", a, b, res, scratch, rows, n, eps, nbytes=8 * a.numel())
         ctx.eps = eps
         ctx.save_for_backward(a, b)
         return res
@@ -1739,10 +1577,7 @@ class _Charbonnier(torch.autograd.Function):
         g = g.contiguous()
         ga = torch.empty_like(a)
         rows = a.shape[0]
-        lib = _hip.lib()
-        _hip.launch("charbonnier_bwd", lambda: _hip.check(lib.savfi_charbonnier_bwd_f32(
-            a.data_ptr(), b.data_ptr(), g.data_ptr(), ga.data_ptr(), rows, a.numel() // rows, ctx.eps, _hip.current_stream()),
-            "savfi_charbonnier_bwd_f32"), nbytes=12 * a.numel())
+        _hip.call("charbonnier_bwd", "savfi_charbonnier_bwd_f32", a, b, g, ga, rows, a.numel() // rows, ctx.eps, nbytes=12 * a.numel())
         gb = -ga if ctx.needs_input_grad[1] else None
         return ga, gb, None
 
@@ -2158,9 +1993,7 @@ def _conv_forward(ctx, x, w, b, stride, padding, dilation, groups, slope, direct
             zb = b if b is not None else torch.zeros(w.shape[:-3], dtype=z.dtype, device=z.device)
             _hip.require_cuda(z, zb)
             rows, chans, hw = z.shape[0] // (T or 1), (T or 1) * Co, z.shape[2] * z.shape[3]      # [n*T,Co] maps = n rows of T*Co channels
-            lib = _hip.lib()
-            _hip.launch("bias_act_fwd", lambda: _hip.check(lib.savfi_bias_act_fwd_f32(
-                z.data_ptr(), zb.data_ptr(), rows, chans, hw, slope, _hip.current_stream()), "savfi_bias_act_fwd_f32"))
+            _hip.call("bias_act_fwd", "savfi_bias_act_fwd_f32", z, zb, rows, chans, hw, slope)
     ctx.route, ctx.T, ctx.conf = route, T, (stride, padding, dilation, groups, slope)
     ctx.in_slope, ctx.defer, ctx.reflect, ctx.gy_unit16 = in_slope, bool(defer), bool(reflect), int(out_unit16) == 2
     ctx.direct, ctx.cache, ctx.w_version, ctx.has_bias = direct, cache, w._version, b is not None
@@ -2217,13 +2050,10 @@ def _conv_backward(ctx, gy):
     gb = torch.empty(w.shape[:-3], dtype=gy.dtype, device=gy.device) if (need_b and not fuse_b) else None
     if gb is not None or not identity:
         rows, chans = N // tasks, tasks * Co                # [n*T,Co] maps = n rows of T*Co channels
-        lib = _hip.lib()
         scratch = (torch.empty(_workspace_floats("savfi_bias_act_scratch_floats", rows, chans, Ho * Wo), dtype=gy.dtype, device=gy.device)
                    if gb is not None else None)
-        _hip.launch("bias_act_bwd", lambda: _hip.check(lib.savfi_bias_act_bwd_f32(
-            gy.data_ptr(), (gy if identity else y).data_ptr(), None if identity else gz.data_ptr(),
-            None if gb is None else gb.data_ptr(), None if scratch is None else scratch.data_ptr(),
-            rows, chans, Ho * Wo, 1.0 if identity else slope, _hip.current_stream()), "savfi_bias_act_bwd_f32"))
+        _hip.call("bias_act_bwd", "savfi_bias_act_bwd_f32", gy, gy if identity else y, None if identity else gz, gb, scratch,
+                  rows, chans, Ho * Wo, 1.0 if identity else slope)
     gx = gw = None
     if need_x and route.dgrad == 'convk':
         if u_bwd is None:
@@ -2336,12 +2166,10 @@ def conv3x3_tasks(x, weight, bias=None, mode=0, slope=1.0, pad=1, f2=False):
     T, Co, Ci = weight.shape[:3]
     assert N % T == 0 and tuple(weight.shape[3:]) == (3, 3) and x.shape[1] == (Ci if mode == 0 else Co), (x.shape, weight.shape, mode)
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, mode)
-    lib = _hip.lib()
     ws = torch.empty(_workspace_floats("savfi_conv3x3_tasks_workspace_floats", N, T, Ci, Co, H, W, int(pad), mode | fbit), dtype=x.dtype, device=x.device)
     out = torch.empty(shape, dtype=x.dtype, device=x.device)
-    _hip.launch(_conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_tasks_f32(
-        x.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), ws.data_ptr(),
-        N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), _hip.current_stream()), "savfi_conv3x3_tasks_f32"), flops=flops)
+    _hip.call(_conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data"), "savfi_conv3x3_tasks_f32", x, weight, bias, out, ws,
+              N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), flops=flops)
     return out
 
 
@@ -2387,7 +2215,6 @@ FilterKind = collections.namedtuple('FilterKind', 'form floats timer single mult
 _WINO = ("savfi_conv3x3_filter_floats", "conv3x3_filters", "savfi_conv3x3_filters_form_f32", "savfi_conv3x3_filters_multi_form_f32")
 _KINDS = {'convk': FilterKind(None, "savfi_convk_filter_floats", "convk_filters", "savfi_convk_filters_f32", "savfi_convk_filters_multi_f32"),
           'wino': FilterKind(0, *_WINO), 'wino2': FilterKind(2, *_WINO)}
-_ptr = lambda t: None if t is None else t.data_ptr()          # (a direction that is not wanted goes to the C ABI as NULL)
 
 
 def _filter_shape(weight):
@@ -2407,8 +2234,8 @@ def _make_filters(kind, weight, fwd, bwd):
     T, Co, Ci, K = _filter_shape(weight)
     us = [torch.empty(_filter_floats(k, T, Ci, Co, K, mode), dtype=torch.float32, device=weight.device) if want else None
           for mode, want in ((0, fwd), (1, bwd))]
-    entry, arg = getattr(_hip.lib(), k.single), (K if k.form is None else k.form)
-    _hip.launch(k.timer, lambda: _hip.check(entry(weight.data_ptr(), _ptr(us[0]), _ptr(us[1]), T, Ci, Co, arg, _raw_stream()), k.single))
+    # (a direction that is not wanted goes to the C ABI as NULL)
+    _hip.call(k.timer, k.single, weight, us[0], us[1], T, Ci, Co, K if k.form is None else k.form, stream=_raw_stream())
     return us[0], us[1]
 
 
@@ -2418,8 +2245,7 @@ def _filters_multi(kind, jobs):
     if not jobs:
         return []
     k, n = _KINDS[kind], len(jobs)
-    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    pw, pf, pb = PA(), PA(), PA()
+    IA = ctypes.c_int * n
     aT, aCi, aCo, aK = IA(), IA(), IA(), IA()
     cuts, total = [], 0
     for j, (w, f, b) in enumerate(jobs):
@@ -2428,13 +2254,9 @@ def _filters_multi(kind, jobs):
         cuts.append((total, total + nf, total + nf + nb))
         total += nf + nb
     flat = torch.empty(total, dtype=torch.float32, device=jobs[0][0].device)
-    made = []
-    for j, ((w, _, _), (start, mid, end)) in enumerate(zip(jobs, cuts)):
-        tf, tb = (flat[start:mid] if mid > start else None), (flat[mid:end] if end > mid else None)
-        pw[j], pf[j], pb[j] = w.data_ptr(), _ptr(tf), _ptr(tb)
-        made.append((tf, tb))
-    entry, arg = getattr(_hip.lib(), k.multi), (aK if k.form is None else IA(*([k.form] * n)))
-    _hip.launch(k.timer + "_multi", lambda: _hip.check(entry(pw, pf, pb, aT, aCi, aCo, arg, n, _raw_stream()), k.multi))
+    made = [((flat[start:mid] if mid > start else None), (flat[mid:end] if end > mid else None)) for start, mid, end in cuts]
+    _hip.call(k.timer + "_multi", k.multi, _hip.ptr_array([w for w, _, _ in jobs]), _hip.ptr_array([tf for tf, _ in made]),
+              _hip.ptr_array([tb for _, tb in made]), aT, aCi, aCo, aK if k.form is None else IA(*([k.form] * n)), n, stream=_raw_stream())
     return made
 
 
@@ -2642,10 +2464,7 @@ def conv3x3_dgrad_in_unit16(gy, u, T, Ci, Co, pad):
     N, _, H, W = gy.shape
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 1)
     out = torch.empty(shape, dtype=gy.dtype, device=gy.device)
-    lib = _hip.lib()
-    _hip.launch(_conv3x3_name(Ci, Co, "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_dgrad_in_unit16_f32(
-        gy.data_ptr(), u.data_ptr(), out.data_ptr(), N, T, Ci, Co, H, W, int(pad), _hip.current_stream()),
-        "savfi_conv3x3_dgrad_in_unit16_f32"), flops=flops)
+    _hip.call(_conv3x3_name(Ci, Co, "bwd_data"), "savfi_conv3x3_dgrad_in_unit16_f32", gy, u, out, N, T, Ci, Co, H, W, int(pad), flops=flops)
     return out
 
 
@@ -2664,21 +2483,17 @@ def conv3x3_tasks_pre(x, u, T, Ci, Co, bias=None, mode=0, slope=1.0, pad=1, mask
     N, _, H, W = x.shape
     assert N % T == 0 and x.shape[1] == (Ci if mode == 0 else Co), (x.shape, T, Ci, Co, mode)
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, mode)
-    lib = _hip.lib()
     if out_unit16:
         assert mode == 0 and not f2
         out = torch.empty(shape, dtype=x.dtype, device=x.device)
-        _hip.launch(_conv3x3_name(Ci, Co, "fwd"), lambda: _hip.check(lib.savfi_conv3x3_tasks_pre_unit16_f32(
-            x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), N, T, Ci, Co, H, W, int(pad), float(slope),
-            _hip.current_stream()), "savfi_conv3x3_tasks_pre_unit16_f32"), flops=flops)
+        _hip.call(_conv3x3_name(Ci, Co, "fwd"), "savfi_conv3x3_tasks_pre_unit16_f32", x, u, bias, out, N, T, Ci, Co, H, W, int(pad),
+                  float(slope), flops=flops)
         return out
     nws = _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, T, Ci, Co, H, W, int(pad), mode | fbit)
     ws = torch.empty(nws, dtype=x.dtype, device=x.device) if nws else None
     out = torch.empty(shape, dtype=x.dtype, device=x.device)
     name = ("conv3x3_" + ("fwd" if mode == 0 else "bwd_data")) if f2 else _conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data")
-    _hip.launch(name, lambda: _hip.check(lib.savfi_conv3x3_tasks_pre_f32(
-        x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), None if ws is None else ws.data_ptr(),
-        N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), _hip.current_stream()), "savfi_conv3x3_tasks_pre_f32"), flops=flops)
+    _hip.call(name, "savfi_conv3x3_tasks_pre_f32", x, u, bias, out, ws, N, T, Ci, Co, H, W, int(pad), mode | fbit, float(slope), flops=flops)
     return out
 
 
@@ -2693,17 +2508,14 @@ def conv3x3_tasks_pre_pool(x, u, T, Ci, Co, bias=None, slope=1.0, pad=1, f2=Fals
     assert N % T == 0 and x.shape[1] == Ci, (x.shape, T, Ci, Co)
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 0)
     assert shape[2] >= 2 and shape[3] >= 2, shape
-    lib = _hip.lib()
     nws = _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, T, Ci, Co, H, W, int(pad), fbit)
     ws = torch.empty(nws, dtype=x.dtype, device=x.device) if nws else None
     out = torch.empty(shape, dtype=x.dtype, device=x.device)
     pooled = torch.empty(shape[:2] + (shape[2] // 2, shape[3] // 2), dtype=x.dtype, device=x.device)
     did = ctypes.c_int(0)
     name = "conv3x3_fwd" if f2 else _conv3x3_name(Ci, Co, "fwd")
-    _hip.launch(name, lambda: _hip.check(lib.savfi_conv3x3_tasks_pre_pool_f32(
-        x.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), pooled.data_ptr(),
-        None if ws is None else ws.data_ptr(), N, T, Ci, Co, H, W, int(pad), fbit, float(slope), ctypes.byref(did), _hip.current_stream()),
-        "savfi_conv3x3_tasks_pre_pool_f32"), flops=flops)
+    _hip.call(name, "savfi_conv3x3_tasks_pre_pool_f32", x, u, bias, out, pooled, ws, N, T, Ci, Co, H, W, int(pad), fbit, float(slope),
+              ctypes.byref(did), flops=flops)
     if not did.value:
         pooled = _avgpool2x2_fwd_launch(out)
     return out, pooled
@@ -2714,12 +2526,10 @@ def _conv3x3_dgrad_masked(gy, u, T, Ci, Co, pad, mask, mask_slope, fbit=0):
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, 1)
     out = torch.empty(shape, dtype=gy.dtype, device=gy.device)
     assert mask.shape == out.shape, (mask.shape, out.shape)
-    lib = _hip.lib()
     nws = _workspace_floats("savfi_conv3x3_tasks_pre_workspace_floats", N, T, Ci, Co, H, W, int(pad), 1 | fbit)
     ws = torch.empty(nws, dtype=gy.dtype, device=gy.device) if nws else None
-    _hip.launch("conv3x3_bwd_data" if fbit else _conv3x3_name(Ci, Co, "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_dgrad_masked_form_f32(
-        gy.data_ptr(), u.data_ptr(), mask.data_ptr(), float(mask_slope), out.data_ptr(), None if ws is None else ws.data_ptr(),
-        N, T, Ci, Co, H, W, int(pad), fbit, _hip.current_stream()), "savfi_conv3x3_dgrad_masked_form_f32"), flops=flops)
+    _hip.call("conv3x3_bwd_data" if fbit else _conv3x3_name(Ci, Co, "bwd_data"), "savfi_conv3x3_dgrad_masked_form_f32", gy, u, mask,
+              float(mask_slope), out, ws, N, T, Ci, Co, H, W, int(pad), fbit, flops=flops)
     return out
 
 
@@ -2731,9 +2541,7 @@ def mask_by_activation(g, y, slope):
     out = torch.empty_like(g)
     N, C = g.shape[:2]
     hw = g.numel() // (N * C)
-    lib = _hip.lib()
-    _hip.launch("bias_act_bwd", lambda: _hip.check(lib.savfi_bias_act_bwd_f32(
-        g.data_ptr(), y.data_ptr(), out.data_ptr(), None, None, N, C, hw, float(slope), _hip.current_stream()), "savfi_bias_act_bwd_f32"))
+    _hip.call("bias_act_bwd", "savfi_bias_act_bwd_f32", g, y, out, None, None, N, C, hw, float(slope))
     return out
 
 
@@ -2769,7 +2577,6 @@ def convk_tasks_pre(x, packed, T, Ci, Co, K, bias=None, mode=0, slope=1.0, pad=1
     I = Co if mode == 0 else Ci
     p_eff = pad if mode == 0 else K - 1 - pad
     out = torch.empty((N, I, H + 2 * p_eff - K + 1, W + 2 * p_eff - K + 1), dtype=x.dtype, device=x.device)
-    lib = _hip.lib()
     if mask is not None and (K != 3 or precise):
         # the masked epilogue exists for the 3 x 3 kernels of the conv chains; the same multiplication as a separate pass elsewhere
         return mask_by_activation(convk_tasks_pre(x, packed, T, Ci, Co, K, bias, mode, slope, pad, precise, reflect), mask, mask_slope)
@@ -2777,14 +2584,12 @@ def convk_tasks_pre(x, packed, T, Ci, Co, K, bias=None, mode=0, slope=1.0, pad=1
         assert mode == 1 and bias is None and slope == 1.0 and not reflect
         mask = mask.contiguous()
         assert mask.shape == out.shape, (mask.shape, out.shape)
-        _hip.launch("convk_bwd_data", lambda: _hip.check(lib.savfi_convk_dgrad_masked_f32(
-            x.data_ptr(), packed.data_ptr(), mask.data_ptr(), float(mask_slope), out.data_ptr(), N, T, Ci, Co, H, W, K, int(pad),
-            int(bool(precise)), _hip.current_stream()), "savfi_convk_dgrad_masked_f32"), flops=2.0 * K * K * Ci * Co * N * H * W)
+        _hip.call("convk_bwd_data", "savfi_convk_dgrad_masked_f32", x, packed, mask, float(mask_slope), out, N, T, Ci, Co, H, W, K, int(pad),
+                  int(bool(precise)), flops=2.0 * K * K * Ci * Co * N * H * W)
         return out
-    _hip.launch("convk_fwd" if mode == 0 else "convk_bwd_data", lambda: _hip.check(lib.savfi_convk_tasks_pre_reflect_f32(
-        x.data_ptr(), packed.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), N, T, Ci, Co, H, W, K, int(pad),
-        mode, float(slope), int(bool(precise)), int(bool(reflect)), _hip.current_stream()), "savfi_convk_tasks_pre_reflect_f32"),
-        flops=2.0 * K * K * Ci * Co * N * (out.shape[2] * out.shape[3] if mode == 0 else H * W))
+    _hip.call("convk_fwd" if mode == 0 else "convk_bwd_data", "savfi_convk_tasks_pre_reflect_f32", x, packed, bias, out, N, T, Ci, Co, H, W,
+              K, int(pad), mode, float(slope), int(bool(precise)), int(bool(reflect)),
+              flops=2.0 * K * K * Ci * Co * N * (out.shape[2] * out.shape[3] if mode == 0 else H * W))
     return out
 
 
@@ -2802,20 +2607,17 @@ def convk_wgrad_tasks(x, gz, T, K, pad, precise=False, reflect=False, want_bias=
     N, Ci, H, W = x.shape
     Co = gz.shape[1]
     assert N % T == 0 and tuple(gz.shape) == (N, Co, H + 2 * pad - K + 1, W + 2 * pad - K + 1), (x.shape, gz.shape, K, pad, T)
-    lib = _hip.lib()
     ws = torch.empty(_workspace_floats("savfi_convk_wgrad_workspace_floats", N, T, Ci, Co, H, W, K, int(pad)), dtype=x.dtype, device=x.device)
     gw = torch.empty((T, Co, Ci, K, K), dtype=x.dtype, device=x.device)
     flops = 2.0 * K * K * Ci * Co * N * gz.shape[2] * gz.shape[3]
     if want_bias:
         assert not precise and convk_wgrad_tasks_sums_bias(x.shape, Co, T, K, pad), "ask convk_wgrad_tasks_sums_bias first"
         gb = torch.empty((T, Co), dtype=x.dtype, device=x.device)
-        _hip.launch("convk_wgrad", lambda: _hip.check(lib.savfi_convk_wgrad_tasks_bias_f32(
-            x.data_ptr(), gz.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), N, T, Ci, Co, H, W, K, int(pad),
-            int(bool(reflect)), _hip.current_stream()), "savfi_convk_wgrad_tasks_bias_f32"), flops=flops)
+        _hip.call("convk_wgrad", "savfi_convk_wgrad_tasks_bias_f32", x, gz, gw, gb, ws, N, T, Ci, Co, H, W, K, int(pad), int(bool(reflect)),
+                  flops=flops)
         return gw, gb
-    _hip.launch("convk_wgrad", lambda: _hip.check(lib.savfi_convk_wgrad_tasks_reflect_f32(
-        x.data_ptr(), gz.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, T, Ci, Co, H, W, K, int(pad), int(bool(precise)),
-        int(bool(reflect)), _hip.current_stream()), "savfi_convk_wgrad_tasks_reflect_f32"), flops=flops)
+    _hip.call("convk_wgrad", "savfi_convk_wgrad_tasks_reflect_f32", x, gz, gw, ws, N, T, Ci, Co, H, W, K, int(pad), int(bool(precise)),
+              int(bool(reflect)), flops=flops)
     return gw
 
 
@@ -2827,18 +2629,13 @@ def reflect_pad_bwd(gp, pad, add=None):
     N, C, Hp, Wp = gp.shape
     H, W = Hp - 2 * pad, Wp - 2 * pad
     gx = torch.empty((N, C, H, W), dtype=gp.dtype, device=gp.device)
-    lib = _hip.lib()
     if add is not None:
         add = add.contiguous()
         _hip.require_cuda(add)
         assert tuple(add.shape) == (N, C, H, W) and add.dtype == gp.dtype, (add.shape, gp.shape, pad)
-        _hip.launch("reflect_pad_bwd", lambda: _hip.check(lib.savfi_reflect_pad_bwd_add_f32(
-            gp.data_ptr(), add.data_ptr(), gx.data_ptr(), N * C, H, W, int(pad), _hip.current_stream()), "savfi_reflect_pad_bwd_add_f32"),
-            nbytes=4 * (gp.numel() + 2 * gx.numel()))
+        _hip.call("reflect_pad_bwd", "savfi_reflect_pad_bwd_add_f32", gp, add, gx, N * C, H, W, int(pad), nbytes=4 * (gp.numel() + 2 * gx.numel()))
         return gx
-    _hip.launch("reflect_pad_bwd", lambda: _hip.check(lib.savfi_reflect_pad_bwd_f32(
-        gp.data_ptr(), gx.data_ptr(), N * C, H, W, int(pad), _hip.current_stream()), "savfi_reflect_pad_bwd_f32"),
-        nbytes=4 * (gp.numel() + gx.numel()))
+    _hip.call("reflect_pad_bwd", "savfi_reflect_pad_bwd_f32", gp, gx, N * C, H, W, int(pad), nbytes=4 * (gp.numel() + gx.numel()))
     return gx
 
 
@@ -2865,10 +2662,7 @@ def _reflect_pad_fwd(x, p):
     if N * C > 65535:          # beyond the launch grid's plane axis: ATen's kernel
         return torch.nn.functional.pad(x, (p,) * 4, mode='reflect')
     xp = torch.empty((N, C, H + 2 * p, W + 2 * p), dtype=x.dtype, device=x.device)
-    lib = _hip.lib()
-    _hip.launch("reflect_pad", lambda: _hip.check(lib.savfi_reflect_pad_fwd_f32(
-        x.data_ptr(), xp.data_ptr(), N * C, H, W, p, _hip.current_stream()), "savfi_reflect_pad_fwd_f32"),
-        nbytes=4 * (x.numel() + xp.numel()))
+    _hip.call("reflect_pad", "savfi_reflect_pad_fwd_f32", x, xp, N * C, H, W, p, nbytes=4 * (x.numel() + xp.numel()))
     return xp
 
 
@@ -2935,7 +2729,6 @@ def conv3x3_wgrad_tasks(x, gz, T, pad=1, stream=None, extra_stream=None, want_bi
     N, Ci, H, W = x.shape
     Co = gz.shape[1]
     assert N % T == 0 and tuple(gz.shape) == (N, Co, H + 2 * pad - 2, W + 2 * pad - 2), (x.shape, gz.shape, pad, T)
-    lib = _hip.lib()
     form = "wino_" if _wgrad_wino(N, Ci, Co, H + 2 * pad - 2, W + 2 * pad - 2) else ""
     gw = torch.empty((T, Co, Ci, 3, 3), dtype=x.dtype, device=x.device)
     if want_bias:
@@ -2945,19 +2738,15 @@ def conv3x3_wgrad_tasks(x, gz, T, pad=1, stream=None, extra_stream=None, want_bi
         if extra_stream is not None:
             for t in (ws, gw, gb):
                 t.record_stream(extra_stream)
-        _hip.launch("conv3x3_wgrad", lambda: _hip.check(lib.savfi_conv3x3_wgrad_wino_tasks_bias_f32(
-            x.data_ptr(), gz.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), N, T, Ci, Co, H, W, int(pad),
-            _hip.current_stream() if stream is None else stream), "savfi_conv3x3_wgrad_wino_tasks_bias_f32"),
-            flops=18.0 * Ci * Co * gz.shape[2] * gz.shape[3] * N)
+        _hip.call("conv3x3_wgrad", "savfi_conv3x3_wgrad_wino_tasks_bias_f32", x, gz, gw, gb, ws, N, T, Ci, Co, H, W, int(pad),
+                  stream=stream, flops=18.0 * Ci * Co * gz.shape[2] * gz.shape[3] * N)
         return gw, gb
     ws = torch.empty(_workspace_floats("savfi_conv3x3_wgrad_%stasks_workspace_floats" % form, N, T, Ci, Co, H, W, int(pad)), dtype=x.dtype, device=x.device)
     if extra_stream is not None:
         ws.record_stream(extra_stream)
         gw.record_stream(extra_stream)
-    entry = "savfi_conv3x3_wgrad_%stasks_f32" % form
-    _hip.launch("conv3x3_wgrad", lambda: _hip.check(getattr(lib, entry)(
-        x.data_ptr(), gz.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, T, Ci, Co, H, W, int(pad),
-        _hip.current_stream() if stream is None else stream), entry), flops=18.0 * Ci * Co * gz.shape[2] * gz.shape[3] * N)
+    _hip.call("conv3x3_wgrad", "savfi_conv3x3_wgrad_%stasks_f32" % form, x, gz, gw, ws, N, T, Ci, Co, H, W, int(pad),
+              stream=stream, flops=18.0 * Ci * Co * gz.shape[2] * gz.shape[3] * N)
     return gw
 
 
@@ -3072,12 +2861,10 @@ def conv3x3(x, weight, bias=None, mode=0, slope=1.0, pad=1):
     Co, Ci = weight.shape[:2]
     assert tuple(weight.shape[2:]) == (3, 3) and x.shape[1] == (Ci if mode == 0 else Co), (x.shape, weight.shape, mode)
     shape, flops = _conv3x3_out(N, Ci, Co, H, W, pad, mode)
-    lib = _hip.lib()
     ws = torch.empty(_workspace_floats("savfi_conv3x3_workspace_floats", N, Ci, Co, H, W, int(pad), mode), dtype=x.dtype, device=x.device)
     out = torch.empty(shape, dtype=x.dtype, device=x.device)
-    _hip.launch(_conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data"), lambda: _hip.check(lib.savfi_conv3x3_f32(
-        x.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), ws.data_ptr(),
-        N, Ci, Co, H, W, int(pad), mode, float(slope), _hip.current_stream()), "savfi_conv3x3_f32"), flops=flops)
+    _hip.call(_conv3x3_name(Ci, Co, "fwd" if mode == 0 else "bwd_data"), "savfi_conv3x3_f32", x, weight, bias, out, ws,
+              N, Ci, Co, H, W, int(pad), mode, float(slope), flops=flops)
     return out
 
 
@@ -3093,15 +2880,13 @@ def conv3x3_wgrad(x, gz, pad=1, stream=None, extra_stream=None):
     assert tuple(gz.shape) == (N, Co, H + 2 * pad - 2, W + 2 * pad - 2), (x.shape, gz.shape, pad)
     if _wgrad_wino(N, Ci, Co, H + 2 * pad - 2, W + 2 * pad - 2):
         return conv3x3_wgrad_tasks(x, gz, 1, pad, stream, extra_stream)[0]
-    lib = _hip.lib()
     ws = torch.empty(_workspace_floats("savfi_conv3x3_wgrad_workspace_floats", N, Ci, Co, H, W, int(pad)), dtype=x.dtype, device=x.device)
     gw = torch.empty((Co, Ci, 3, 3), dtype=x.dtype, device=x.device)
     if extra_stream is not None:
         ws.record_stream(extra_stream)
         gw.record_stream(extra_stream)
-    _hip.launch("conv3x3_wgrad", lambda: _hip.check(lib.savfi_conv3x3_wgrad_f32(
-        x.data_ptr(), gz.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, Ci, Co, H, W, int(pad),
-        _hip.current_stream() if stream is None else stream), "savfi_conv3x3_wgrad_f32"), flops=18.0 * Ci * Co * gz.shape[2] * gz.shape[3] * N)
+    _hip.call("conv3x3_wgrad", "savfi_conv3x3_wgrad_f32", x, gz, gw, ws, N, Ci, Co, H, W, int(pad), stream=stream,
+              flops=18.0 * Ci * Co * gz.shape[2] * gz.shape[3] * N)
     return gw
 
 
@@ -3135,24 +2920,17 @@ class _ChannelAttentionResidual(torch.autograd.Function):
         N, C, H, W = t.shape
         T, Cr = w1.shape[0], w1.shape[1]
         assert x.shape == t.shape and N % T == 0 and tuple(w1.shape) == (T, Cr, C) and tuple(w2.shape) == (T, C, Cr), (t.shape, w1.shape, w2.shape)
-        lib = _hip.lib()
-        st = _hip.current_stream()
         s = torch.empty((N, C), dtype=t.dtype, device=t.device)
         y = torch.empty((N, C), dtype=t.dtype, device=t.device)
         a1 = torch.empty((N, Cr), dtype=t.dtype, device=t.device)
         out = torch.empty_like(t)
         hw = H * W
-        _hip.launch("ca_pool", lambda: _hip.check(lib.savfi_ca_pool_f32(t.data_ptr(), None, s.data_ptr(), N * C, hw, 1.0 / hw, st),
-                                                  "savfi_ca_pool_f32"), nbytes=4 * t.numel())
+        _hip.call("ca_pool", "savfi_ca_pool_f32", t, None, s, N * C, hw, 1.0 / hw, nbytes=4 * t.numel())
         if CA_FUSE_MLP and Cr <= 16 and C <= 256:       # the MLP inside the apply launch (every workgroup repeats it for its sample: the same y, bit for bit)
-            _hip.launch("ca_apply", lambda: _hip.check(lib.savfi_ca_apply_mlp_f32(
-                t.data_ptr(), s.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), x.data_ptr(), out.data_ptr(),
-                y.data_ptr(), a1.data_ptr(), N, T, C, Cr, hw, st), "savfi_ca_apply_mlp_f32"), nbytes=12 * t.numel())
+            _hip.call("ca_apply", "savfi_ca_apply_mlp_f32", t, s, w1, b1, w2, b2, x, out, y, a1, N, T, C, Cr, hw, nbytes=12 * t.numel())
         else:
-            _hip.launch("ca_mlp", lambda: _hip.check(lib.savfi_ca_mlp_fwd_f32(s.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                                                              y.data_ptr(), a1.data_ptr(), N, T, C, Cr, st), "savfi_ca_mlp_fwd_f32"))
-            _hip.launch("ca_apply", lambda: _hip.check(lib.savfi_ca_apply_f32(t.data_ptr(), y.data_ptr(), x.data_ptr(), None, out.data_ptr(), N * C, hw, st),
-                                                       "savfi_ca_apply_f32"), nbytes=12 * t.numel())
+            _hip.call("ca_mlp", "savfi_ca_mlp_fwd_f32", s, w1, b1, w2, b2, y, a1, N, T, C, Cr)
+            _hip.call("ca_apply", "savfi_ca_apply_f32", t, y, x, None, out, N * C, hw, nbytes=12 * t.numel())
         ctx.save_for_backward(t, s, y, a1, w1, w2)
         ctx.mark_non_differentiable(y)
         ctx.set_materialize_grads(False)        # (else autograd fills a zero tensor for the attention's cotangent on every backward call)
@@ -3168,25 +2946,18 @@ class _ChannelAttentionResidual(torch.autograd.Function):
         N, C, H, W = t.shape
         T, Cr = w1.shape[0], w1.shape[1]
         hw = H * W
-        lib = _hip.lib()
-        st = _hip.current_stream()
         r = torch.empty((N, C), dtype=t.dtype, device=t.device)
         ds = torch.empty((N, C), dtype=t.dtype, device=t.device)
         gw1, gb1 = torch.empty_like(w1), torch.empty((T, Cr), dtype=t.dtype, device=t.device)
         gw2, gb2 = torch.empty_like(w2), torch.empty((T, C), dtype=t.dtype, device=t.device)
         gt = torch.empty_like(t)
-        _hip.launch("ca_pool", lambda: _hip.check(lib.savfi_ca_pool_f32(g.data_ptr(), t.data_ptr(), r.data_ptr(), N * C, hw, 1.0, st),
-                                                  "savfi_ca_pool_f32"), nbytes=8 * t.numel())
+        _hip.call("ca_pool", "savfi_ca_pool_f32", g, t, r, N * C, hw, 1.0, nbytes=8 * t.numel())
         if CA_FUSE_MLP and Cr <= 16 and C <= 256:       # the MLP's backward inside the apply launch: ds per workgroup, the parameter gradients from T workgroups
-            _hip.launch("ca_apply", lambda: _hip.check(lib.savfi_ca_apply_bwd_mlp_f32(             # at the front of its grid
-                g.data_ptr(), r.data_ptr(), s.data_ptr(), y.data_ptr(), a1.data_ptr(), w1.data_ptr(), w2.data_ptr(), gt.data_ptr(), gw1.data_ptr(),
-                gb1.data_ptr(), gw2.data_ptr(), gb2.data_ptr(), N, T, C, Cr, hw, st), "savfi_ca_apply_bwd_mlp_f32"), nbytes=8 * t.numel())
+            _hip.call("ca_apply", "savfi_ca_apply_bwd_mlp_f32", g, r, s, y, a1, w1, w2, gt, gw1, gb1, gw2, gb2, N, T, C, Cr, hw,       # at the front of its grid
+                      nbytes=8 * t.numel())
         else:
-            _hip.launch("ca_mlp_bwd", lambda: _hip.check(lib.savfi_ca_mlp_bwd_f32(
-                r.data_ptr(), s.data_ptr(), y.data_ptr(), a1.data_ptr(), w1.data_ptr(), w2.data_ptr(), ds.data_ptr(), gw1.data_ptr(), gb1.data_ptr(),
-                gw2.data_ptr(), gb2.data_ptr(), N, T, C, Cr, 1.0 / hw, st), "savfi_ca_mlp_bwd_f32"))
-            _hip.launch("ca_apply", lambda: _hip.check(lib.savfi_ca_apply_f32(g.data_ptr(), y.data_ptr(), None, ds.data_ptr(), gt.data_ptr(), N * C, hw, st),
-                                                       "savfi_ca_apply_f32"), nbytes=8 * t.numel())
+            _hip.call("ca_mlp_bwd", "savfi_ca_mlp_bwd_f32", r, s, y, a1, w1, w2, ds, gw1, gb1, gw2, gb2, N, T, C, Cr, 1.0 / hw)
+            _hip.call("ca_apply", "savfi_ca_apply_f32", g, y, None, ds, gt, N * C, hw, nbytes=8 * t.numel())
         need = ctx.needs_input_grad
         return (gt if need[0] else None, g if need[1] else None, gw1 if need[2] else None, gb1 if need[3] else None,
                 gw2 if need[4] else None, gb2 if need[5] else None)
@@ -3218,10 +2989,8 @@ class _Upsample2x(torch.autograd.Function):
         H, W, sy0, sx0, Hs, Ws, oy0, ox0, Hw, Ww = geom
         assert tuple(x.shape[2:]) == (Hs, Ws), (x.shape, geom)
         out = torch.empty((N, C, Hw, Ww), dtype=x.dtype, device=x.device)
-        lib = _hip.lib()
-        _hip.launch("upsample2x_fwd", lambda: _hip.check(lib.savfi_upsample2x_window_fwd_f32(
-            x.data_ptr(), out.data_ptr(), N * C, *geom, int(align_corners), _hip.current_stream()),
-            "savfi_upsample2x_window_fwd_f32"), nbytes=4 * N * C * (Hs * Ws + Hw * Ww))
+        _hip.call("upsample2x_fwd", "savfi_upsample2x_window_fwd_f32", x, out, N * C, *geom, int(align_corners),
+                  nbytes=4 * N * C * (Hs * Ws + Hw * Ww))
         ctx.align, ctx.geom, ctx.in_slope = bool(align_corners), geom, in_slope
         if in_slope is not None:
             ctx.save_for_backward(x)
@@ -3239,10 +3008,8 @@ class _Upsample2x(torch.autograd.Function):
             N, C = g.shape[:2]
             H, W, sy0, sx0, Hs, Ws, oy0, ox0, Hw, Ww = ctx.geom
             gin = torch.empty((N, C, Hs, Ws), dtype=g.dtype, device=g.device)
-            lib = _hip.lib()
-            _hip.launch("upsample2x_bwd", lambda: _hip.check(lib.savfi_upsample2x_window_bwd_masked_f32(
-                g.data_ptr(), x.data_ptr(), float(ctx.in_slope), gin.data_ptr(), N * C, *ctx.geom, int(ctx.align), _hip.current_stream()),
-                "savfi_upsample2x_window_bwd_masked_f32"), nbytes=4 * N * C * (2 * Hs * Ws + Hw * Ww))
+            _hip.call("upsample2x_bwd", "savfi_upsample2x_window_bwd_masked_f32", g, x, float(ctx.in_slope), gin, N * C, *ctx.geom,
+                      int(ctx.align), nbytes=4 * N * C * (2 * Hs * Ws + Hw * Ww))
             return gin, None, None, None
         # linear op: its adjoint goes through the Function too, so double-backward keeps working
         return _Upsample2xAdjoint.apply(g, ctx.align, ctx.geom), None, None, None
@@ -3257,10 +3024,8 @@ class _Upsample2xAdjoint(torch.autograd.Function):
         H, W, sy0, sx0, Hs, Ws, oy0, ox0, Hw, Ww = geom
         assert tuple(g.shape[2:]) == (Hw, Ww), (g.shape, geom)
         gin = torch.empty((N, C, Hs, Ws), dtype=g.dtype, device=g.device)
-        lib = _hip.lib()
-        _hip.launch("upsample2x_bwd", lambda: _hip.check(lib.savfi_upsample2x_window_bwd_f32(
-            g.data_ptr(), gin.data_ptr(), N * C, *geom, int(align_corners), _hip.current_stream()),
-            "savfi_upsample2x_window_bwd_f32"), nbytes=4 * N * C * (Hs * Ws + Hw * Ww))
+        _hip.call("upsample2x_bwd", "savfi_upsample2x_window_bwd_f32", g, gin, N * C, *geom, int(align_corners),
+                  nbytes=4 * N * C * (Hs * Ws + Hw * Ww))
         ctx.align, ctx.geom = bool(align_corners), geom
         return gin
 

@@ -36,10 +36,10 @@ def msssim_loss_per_sample(sr, hr):
     return 1 - hip_ops.msssim_per_sample(sr, hr, normalize=True)
 
 
-_KERNELS = {'L1': hip_ops.l1_loss, 'MSE': hip_ops.mse_loss, 'SSIM': hip_ops.ssim_loss, 'MSSSIM': msssim_loss, 'Lap': hip_ops.lap_loss,
-            'Census': hip_ops.census_loss}
-_KERNELS_PER_SAMPLE = {'L1': hip_ops.l1_loss_per_sample, 'MSE': hip_ops.mse_loss_per_sample, 'SSIM': hip_ops.ssim_loss_per_sample,
-                       'MSSSIM': msssim_loss_per_sample, 'Lap': hip_ops.lap_loss_per_sample, 'Census': hip_ops.census_loss_per_sample}
+# TYPE -> (one value over the batch, [N]: every sample on its own)
+_KERNELS = {'L1': (hip_ops.l1_loss, hip_ops.l1_loss_per_sample), 'MSE': (hip_ops.mse_loss, hip_ops.mse_loss_per_sample),
+            'SSIM': (hip_ops.ssim_loss, hip_ops.ssim_loss_per_sample), 'MSSSIM': (msssim_loss, msssim_loss_per_sample),
+            'Lap': (hip_ops.lap_loss, hip_ops.lap_loss_per_sample), 'Census': (hip_ops.census_loss, hip_ops.census_loss_per_sample)}
 
 
 class Loss(nn.modules.loss._Loss):
@@ -51,34 +51,31 @@ class Loss(nn.modules.loss._Loss):
             if loss_type not in _KERNELS:
                 raise NotImplementedError(
                     "loss '%s' is outside the inner-loop path built here (only L1, MSE; 'Super' / VGG terms need pretrained VGG16 weights)" % loss_type)
-            self.loss.append({'type': loss_type, 'weight': float(weight), 'function': _KERNELS[loss_type]})
+            self.loss.append({'type': loss_type, 'weight': float(weight), 'function': _KERNELS[loss_type][0]})
         self.cuda_only = True
 
     def loss_keys(self):
         """Keys of the dict forward() returns (rank-independent: the logging all-reduce is laid out from them)."""
         return [l['type'] for l in self.loss] + ['total']
 
-    def per_sample(self, sr, hr):
-        """The same terms for every sample of a batch on its own: {TYPE: [N], 'total': [N]} (tasks adapted in lockstep:
-        the reference evaluates the criterion once per task on N=1 tensors, meta_learning_system.py:389-395)."""
+    def _terms(self, sr, hr, per_sample):
+        """{TYPE: weight * term, ..., 'total': their sum}, the terms over the batch or per sample."""
         total = 0
         losses = {}
         for l in self.loss:
-            eff = l['weight'] * _KERNELS_PER_SAMPLE[l['type']](sr, hr)
+            eff = l['weight'] * (_KERNELS[l['type']][1] if per_sample else l['function'])(sr, hr)
             losses[l['type']] = eff
             total = total + eff
         losses['total'] = total
         return losses
 
+    def per_sample(self, sr, hr):
+        """The same terms for every sample of a batch on its own: {TYPE: [N], 'total': [N]} (tasks adapted in lockstep:
+        the reference evaluates the criterion once per task on N=1 tensors, meta_learning_system.py:389-395)."""
+        return self._terms(sr, hr, True)
+
     def forward(self, sr, hr, **kwargs):
-        total = 0
-        losses = {}
-        for l in self.loss:
-            eff = l['weight'] * l['function'](sr, hr)
-            losses[l['type']] = eff
-            total = total + eff
-        losses['total'] = total
-        return losses
+        return self._terms(sr, hr, False)
 
 
 class CharbonnierLoss(nn.modules.loss._Loss):

@@ -35,9 +35,7 @@ def frames8_supported(frame, B, C, Ho, Wo, K, tap_bstride=None):
 def frames8_classify(frame):
     """int32[FRAMES8_WORDS] on the frame's device: all zero = every element of `frame` is the fp32 quotient k / 255, k = 0..255"""
     cls = torch.empty(FRAMES8_WORDS, dtype=torch.int32, device=frame.device)
-    lib = _hip.lib()
-    _hip.launch("frames8_classify", lambda: _hip.check(lib.savfi_frames8_classify_f32(
-        frame.data_ptr(), frame.numel(), cls.data_ptr(), _hip.current_stream()), "savfi_frames8_classify_f32"), nbytes=4 * frame.numel())
+    _hip.call("frames8_classify", "savfi_frames8_classify_f32", frame, frame.numel(), cls, nbytes=4 * frame.numel())
     return cls
 
 
@@ -59,95 +57,82 @@ def _dims(input, vertical, horizontal):
     return B, C, Ho, Wo, K
 
 
+def _sepconv_fwd(input, vertical, horizontal, try_frames8):
+    """The forward launches of FunctionSepconv and FunctionSepconvTwice (which have checked their arguments) -> (output, cls).  With
+    `try_frames8`, where frames8_supported says yes and the library takes the call: the 8-bit-frame kernels, cls = the frame's class
+    words for the backward; else the six-product kernel, cls = None."""
+    B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+    output = torch.empty((B, C, Ho, Wo), dtype=input.dtype, device=input.device)
+    nbytes = algorithmic_bytes(B, C, Ho, Wo, K)
+    if try_frames8 and frames8_supported(input, B, C, Ho, Wo, K):
+        cls = frames8_classify(input)
+        entry, rc = _hip.lib().savfi_sepconv_fwd_frames8_f32, [0]
+
+        def run8():     # the one launch whose return code is not simply checked (_hip.call): SAVFI_E_UNSUPPORTED falls through to the six products
+            rc[0] = entry(input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(), cls.data_ptr(),
+                          B, C, Ho, Wo, K, K, 0, _hip.current_stream())
+            if rc[0] != _E_UNSUPPORTED:
+                _hip.check(rc[0], "savfi_sepconv_fwd_frames8_f32")
+        _hip.launch("sepconv_fwd", run8, nbytes=nbytes)
+        if rc[0] != _E_UNSUPPORTED:
+            return output, cls
+    _hip.call("sepconv_fwd", "savfi_sepconv_fwd_f32", input, vertical, horizontal, output, B, C, Ho, Wo, K, nbytes=nbytes)
+    return output, None
+
+
+def _sepconv_grads(input, vertical, horizontal, gradOutput, cls, need_v, need_h, need_i=False):
+    """The first-order gradient launch of FunctionSepconv.backward and _SepconvFilterGrads -> (gI, gV, gH), None where not asked for
+    (gradOutput contiguous).  The 8-bit-frame kernels where the forward classified the frame (cls) and exactly the two tap gradients
+    are wanted, else the six-product kernel, under the timer name "sepconv_bwd+gI" when it produces gI."""
+    B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+    gI = torch.empty_like(input) if need_i else None
+    gV = torch.empty_like(vertical) if need_v else None
+    gH = torch.empty_like(horizontal) if need_h else None
+    if cls is not None and need_v and need_h and not need_i:
+        _hip.call("sepconv_bwd", "savfi_sepconv_bwd_frames8_f32", input, vertical, horizontal, gradOutput, gV, gH, cls,
+                  B, C, Ho, Wo, K, K, 0, nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
+    elif need_i or need_v or need_h:
+        _hip.call("sepconv_bwd" if not need_i else "sepconv_bwd+gI", "savfi_sepconv_bwd_f32", input, vertical, horizontal, gradOutput,
+                  gI, gV, gH, B, C, Ho, Wo, K, nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=int(need_v) + int(need_h)))
+    return gI, gV, gH
+
+
 class FunctionSepconv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, vertical, horizontal):
-        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+        _dims(input, vertical, horizontal)
         assert input.is_contiguous() and vertical.is_contiguous() and horizontal.is_contiguous()
         if not input.is_cuda:
             raise NotImplementedError("FunctionSepconv has no CPU path (neither does the reference)")
         _hip.require_cuda(input, vertical, horizontal)
-        output = torch.empty((B, C, Ho, Wo), dtype=input.dtype, device=input.device)
-        lib = _hip.lib()
-        cls = None
-        if not ctx.needs_input_grad[0] and frames8_supported(input, B, C, Ho, Wo, K):
-            cls = frames8_classify(input)
-            rc = [0]
-
-            def run8():
-                rc[0] = lib.savfi_sepconv_fwd_frames8_f32(input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
-                                                          cls.data_ptr(), B, C, Ho, Wo, K, K, 0, _hip.current_stream())
-                if rc[0] != _E_UNSUPPORTED:
-                    _hip.check(rc[0], "savfi_sepconv_fwd_frames8_f32")
-            _hip.launch("sepconv_fwd", run8, nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
-            if rc[0] == _E_UNSUPPORTED:
-                cls = None
-        if cls is None:
-            _hip.launch("sepconv_fwd", lambda: _hip.check(lib.savfi_sepconv_fwd_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
-                B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_fwd_f32"),
-                nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
-            ctx.save_for_backward(input, vertical, horizontal)
-        else:
-            ctx.save_for_backward(input, vertical, horizontal, cls)
+        output, cls = _sepconv_fwd(input, vertical, horizontal, not ctx.needs_input_grad[0])
+        ctx.save_for_backward(input, vertical, horizontal, *(() if cls is None else (cls,)))
         return output
 
     @staticmethod
     def backward(ctx, gradOutput):
         input, vertical, horizontal = ctx.saved_tensors[:3]
         cls = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
-        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
         if not gradOutput.is_contiguous():
             gradOutput = gradOutput.contiguous()
         if not input.is_cuda:
             raise NotImplementedError("FunctionSepconv has no CPU path (neither does the reference)")
         _hip.require_cuda(gradOutput)
         need_i, need_v, need_h = ctx.needs_input_grad
-        gI = torch.empty_like(input) if need_i else None
-        gV = torch.empty_like(vertical) if need_v else None
-        gH = torch.empty_like(horizontal) if need_h else None
-        if cls is not None and need_v and need_h and not need_i:
-            lib = _hip.lib()
-            _hip.launch("sepconv_bwd", lambda: _hip.check(lib.savfi_sepconv_bwd_frames8_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(), gV.data_ptr(), gH.data_ptr(),
-                cls.data_ptr(), B, C, Ho, Wo, K, K, 0, _hip.current_stream()), "savfi_sepconv_bwd_frames8_f32"),
-                nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
-        elif need_i or need_v or need_h:
-            lib = _hip.lib()
-            p = lambda t: None if t is None else t.data_ptr()
-            name = "sepconv_bwd" if not need_i else "sepconv_bwd+gI"
-            _hip.launch(name, lambda: _hip.check(lib.savfi_sepconv_bwd_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(),
-                p(gI), p(gV), p(gH), B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_bwd_f32"),
-                nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=int(need_v) + int(need_h)))
-        return gI, gV, gH
+        return _sepconv_grads(input, vertical, horizontal, gradOutput, cls, need_v, need_h, need_i)
 
 
 class _SepconvFilterGrads(torch.autograd.Function):
     """(input, vertical, horizontal, gradOutput[, cls]) -> (gradVertical, gradHorizontal): the backward of FunctionSepconvTwice as a
-    function of its own, through the entry points FunctionSepconv.backward uses.  Its backward is savfi_sepconv_bwd2_f32
+    function of its own, through the launch FunctionSepconv.backward runs (_sepconv_grads).  Its backward is savfi_sepconv_bwd2_f32
     (csrc/sepconv_bwd2.hip) and is once differentiable: a third derivative raises."""
 
     @staticmethod
     def forward(ctx, input, vertical, horizontal, gradOutput, cls, need_v, need_h):
-        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
         if not gradOutput.is_contiguous():
             gradOutput = gradOutput.contiguous()
         _hip.require_cuda(gradOutput)
-        gV = torch.empty_like(vertical) if need_v else None
-        gH = torch.empty_like(horizontal) if need_h else None
-        lib = _hip.lib()
-        if cls is not None and need_v and need_h:
-            _hip.launch("sepconv_bwd", lambda: _hip.check(lib.savfi_sepconv_bwd_frames8_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(), gV.data_ptr(), gH.data_ptr(),
-                cls.data_ptr(), B, C, Ho, Wo, K, K, 0, _hip.current_stream()), "savfi_sepconv_bwd_frames8_f32"),
-                nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
-        elif need_v or need_h:
-            p = lambda t: None if t is None else t.data_ptr()
-            _hip.launch("sepconv_bwd", lambda: _hip.check(lib.savfi_sepconv_bwd_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(),
-                None, p(gV), p(gH), B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_bwd_f32"),
-                nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=int(need_v) + int(need_h)))
+        _, gV, gH = _sepconv_grads(input, vertical, horizontal, gradOutput, cls, need_v, need_h)
         ctx.save_for_backward(input, vertical, horizontal, gradOutput)
         ctx.have = (need_v, need_h)
         return gV, gH
@@ -166,13 +151,10 @@ class _SepconvFilterGrads(torch.autograd.Function):
         dH = torch.empty_like(horizontal) if need_h and ggV is not None else None
         if d_gO is not None or dV is not None or dH is not None:
             _hip.require_cuda(*[t for t in (ggV, ggH) if t is not None])
-            lib = _hip.lib()
-            p = lambda t: None if t is None else t.data_ptr()
             n_out = sum(t is not None for t in (dV, dH))
-            _hip.launch("sepconv_bwd2", lambda: _hip.check(lib.savfi_sepconv_bwd2_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradOutput.data_ptr(), p(ggV), p(ggH),
-                p(d_gO), p(dV), p(dH), B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_bwd2_f32"),
-                nbytes=bwd2_algorithmic_bytes(B, C, Ho, Wo, K, int(ggV is not None) + int(ggH is not None), d_gO is not None, n_out))
+            _hip.call("sepconv_bwd2", "savfi_sepconv_bwd2_f32", input, vertical, horizontal, gradOutput, ggV, ggH, d_gO, dV, dH,
+                      B, C, Ho, Wo, K,
+                      nbytes=bwd2_algorithmic_bytes(B, C, Ho, Wo, K, int(ggV is not None) + int(ggH is not None), d_gO is not None, n_out))
         return None, dV, dH, d_gO, None, None, None
 
 
@@ -194,7 +176,7 @@ class FunctionSepconvTwice(torch.autograd.Function):
 
         FunctionSepconvTwice.apply(input[B,C,Ho+K-1,Wo+K-1], vertical[B,K,Ho,Wo], horizontal[B,K,Ho,Wo]) -> output[B,C,Ho,Wo]
 
-    The forward and the first-order gradients go through the entry points of FunctionSepconv: same bits.  The backward is itself an
+    The forward and the first-order gradients are the launches of FunctionSepconv (_sepconv_fwd, _sepconv_grads): same bits.  The backward is itself an
     autograd.Function (_SepconvFilterGrads), so under create_graph=True the tap gradients carry a graph and the second-order terms
     of MAML -- which FunctionSepconv, like the reference's op, drops silently -- reach the outer gradient through
     savfi_sepconv_bwd2_f32.  A frame that requires grad is refused: the second-order terms of gI are not built, and an op that
@@ -205,34 +187,13 @@ class FunctionSepconvTwice(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("FunctionSepconvTwice: the frame requires grad, and the second-order terms of the input gradient "
                                       "are not implemented (they would be dropped silently); use FunctionSepconv for gI")
-        B, C, Ho, Wo, K = _dims(input, vertical, horizontal)
+        _dims(input, vertical, horizontal)
         assert input.is_contiguous() and vertical.is_contiguous() and horizontal.is_contiguous()
         if not input.is_cuda:
             raise NotImplementedError("FunctionSepconvTwice has no CPU path (neither does the reference's op)")
         _hip.require_cuda(input, vertical, horizontal)
-        output = torch.empty((B, C, Ho, Wo), dtype=input.dtype, device=input.device)
-        lib = _hip.lib()
-        cls = None
-        if frames8_supported(input, B, C, Ho, Wo, K):
-            cls = frames8_classify(input)
-            rc = [0]
-
-            def run8():
-                rc[0] = lib.savfi_sepconv_fwd_frames8_f32(input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
-                                                          cls.data_ptr(), B, C, Ho, Wo, K, K, 0, _hip.current_stream())
-                if rc[0] != _E_UNSUPPORTED:
-                    _hip.check(rc[0], "savfi_sepconv_fwd_frames8_f32")
-            _hip.launch("sepconv_fwd", run8, nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
-            if rc[0] == _E_UNSUPPORTED:
-                cls = None
-        if cls is None:
-            _hip.launch("sepconv_fwd", lambda: _hip.check(lib.savfi_sepconv_fwd_f32(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
-                B, C, Ho, Wo, K, _hip.current_stream()), "savfi_sepconv_fwd_f32"),
-                nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
-            ctx.save_for_backward(input, vertical, horizontal)
-        else:
-            ctx.save_for_backward(input, vertical, horizontal, cls)
+        output, cls = _sepconv_fwd(input, vertical, horizontal, True)       # (a frame that requires grad has been refused above)
+        ctx.save_for_backward(input, vertical, horizontal, *(() if cls is None else (cls,)))
         return output
 
     @staticmethod
@@ -282,7 +243,6 @@ class FunctionSepconvPair(torch.autograd.Function):
         from ... import hip_ops
         hip_ops.require_layout(taps, hip_ops.UNIT16 if taps_unit16 else None, "FunctionSepconvPair(taps_unit16=%s): taps" % bool(taps_unit16))
         _hip.require_cuda(input0, input1, taps)
-        lib, st = _hip.lib(), _hip.current_stream()
         plane = K * Ho * Wo * 4
         words = [frames8_classify(inp) for inp in (input0, input1)] if frames8_supported(input0, B, C, Ho, Wo, K, 4 * K) else None
         u16 = 1 if taps_unit16 else 0
@@ -294,22 +254,20 @@ class FunctionSepconvPair(torch.autograd.Function):
         if ctx.pair:
             # ONE launch for both local convolutions (2 B virtual samples; see backward): out2[b, f] = the convolution of frame f
             out2 = torch.empty((B, 2, C, Ho, Wo), dtype=input0.dtype, device=input0.device)
-            _hip.launch("sepconv_fwd", lambda: _hip.check(lib.savfi_sepconv_fwd_pair_frames8_f32(
-                input0.data_ptr(), input1.data_ptr(), taps.data_ptr(), out2.data_ptr(), words[0].data_ptr(), words[1].data_ptr(),
-                B, C, Ho, Wo, K, u16, st), "savfi_sepconv_fwd_pair_frames8_f32"), nbytes=2 * algorithmic_bytes(B, C, Ho, Wo, K))
+            _hip.call("sepconv_fwd", "savfi_sepconv_fwd_pair_frames8_f32", input0, input1, taps, out2, words[0], words[1],
+                      B, C, Ho, Wo, K, u16, nbytes=2 * algorithmic_bytes(B, C, Ho, Wo, K))
             ctx.save_for_backward(input0, input1, taps, *words)
             return out2[:, 0].add(out2[:, 1])
         out0 = torch.empty((B, C, Ho, Wo), dtype=input0.dtype, device=input0.device)
         out1 = torch.empty_like(out0)
         for i, (inp, out, s) in enumerate(((input0, out0, 0), (input1, out1, 2))):
+            tv, th = taps.data_ptr() + s * plane, taps.data_ptr() + (s + 1) * plane
             if words is not None:
-                _hip.launch("sepconv_fwd", lambda inp=inp, out=out, s=s, i=i: _hip.check(lib.savfi_sepconv_fwd_frames8_f32(
-                    inp.data_ptr(), taps.data_ptr() + s * plane, taps.data_ptr() + (s + 1) * plane, out.data_ptr(), words[i].data_ptr(),
-                    B, C, Ho, Wo, K, 4 * K, u16, st), "savfi_sepconv_fwd_frames8_f32"), nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
+                _hip.call("sepconv_fwd", "savfi_sepconv_fwd_frames8_f32", inp, tv, th, out, words[i], B, C, Ho, Wo, K, 4 * K, u16,
+                          nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
             else:
-                _hip.launch("sepconv_fwd", lambda inp=inp, out=out, s=s: _hip.check(lib.savfi_sepconv_fwd_taps_strided_f32(
-                    inp.data_ptr(), taps.data_ptr() + s * plane, taps.data_ptr() + (s + 1) * plane, out.data_ptr(),
-                    B, C, Ho, Wo, K, 4 * K, st), "savfi_sepconv_fwd_taps_strided_f32"), nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
+                _hip.call("sepconv_fwd", "savfi_sepconv_fwd_taps_strided_f32", inp, tv, th, out, B, C, Ho, Wo, K, 4 * K,
+                          nbytes=algorithmic_bytes(B, C, Ho, Wo, K))
         ctx.save_for_backward(input0, input1, taps, *(words or ()))
         return out0.add_(out1)
 
@@ -326,28 +284,23 @@ class FunctionSepconvPair(torch.autograd.Function):
         _hip.require_cuda(gradOutput)
         from ... import hip_ops
         gT = torch.empty_like(taps)
-        lib, st = _hip.lib(), _hip.current_stream()
         plane = K * Ho * Wo * 4
         if ctx.pair:
             # ONE launch for both local convolutions (2 B virtual samples): a launch of these kernels has a fixed cost of ~24 us
-            _hip.launch("sepconv_bwd", lambda: _hip.check(lib.savfi_sepconv_bwd_pair_frames8_f32(
-                input0.data_ptr(), input1.data_ptr(), taps.data_ptr(), gradOutput.data_ptr(), gT.data_ptr(), words[0].data_ptr(),
-                words[1].data_ptr(), B, C, Ho, Wo, K, ctx.taps_unit16, st), "savfi_sepconv_bwd_pair_frames8_f32"),
-                nbytes=2 * algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
+            _hip.call("sepconv_bwd", "savfi_sepconv_bwd_pair_frames8_f32", input0, input1, taps, gradOutput, gT, words[0], words[1],
+                      B, C, Ho, Wo, K, ctx.taps_unit16, nbytes=2 * algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
             if ctx.taps_unit16 & 2:
                 hip_ops.tag_layout(gT, hip_ops.UNIT16)
             return None, None, gT, None, None
         for i, (inp, s) in enumerate(((input0, 0), (input1, 2))):
+            tv, th = taps.data_ptr() + s * plane, taps.data_ptr() + (s + 1) * plane
+            gv, gh = gT.data_ptr() + s * plane, gT.data_ptr() + (s + 1) * plane
             if words is not None:
-                _hip.launch("sepconv_bwd", lambda inp=inp, s=s, i=i: _hip.check(lib.savfi_sepconv_bwd_frames8_f32(
-                    inp.data_ptr(), taps.data_ptr() + s * plane, taps.data_ptr() + (s + 1) * plane, gradOutput.data_ptr(),
-                    gT.data_ptr() + s * plane, gT.data_ptr() + (s + 1) * plane, words[i].data_ptr(), B, C, Ho, Wo, K, 4 * K, ctx.taps_unit16, st),
-                    "savfi_sepconv_bwd_frames8_f32"), nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
+                _hip.call("sepconv_bwd", "savfi_sepconv_bwd_frames8_f32", inp, tv, th, gradOutput, gv, gh, words[i],
+                          B, C, Ho, Wo, K, 4 * K, ctx.taps_unit16, nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
             else:
-                _hip.launch("sepconv_bwd", lambda inp=inp, s=s: _hip.check(lib.savfi_sepconv_bwd_taps_strided_f32(
-                    inp.data_ptr(), taps.data_ptr() + s * plane, taps.data_ptr() + (s + 1) * plane, gradOutput.data_ptr(),
-                    gT.data_ptr() + s * plane, gT.data_ptr() + (s + 1) * plane, B, C, Ho, Wo, K, 4 * K, st),
-                    "savfi_sepconv_bwd_taps_strided_f32"), nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
+                _hip.call("sepconv_bwd", "savfi_sepconv_bwd_taps_strided_f32", inp, tv, th, gradOutput, gv, gh, B, C, Ho, Wo, K, 4 * K,
+                          nbytes=algorithmic_bytes(B, C, Ho, Wo, K, grads=2))
         if ctx.taps_unit16 & 2:
             hip_ops.tag_layout(gT, hip_ops.UNIT16)
         return None, None, gT, None, None

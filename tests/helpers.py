@@ -1,5 +1,6 @@
 """Shared test helpers (CPU side): build oracle inputs from the seeded recipe, read golden fixtures."""
 import ast
+import contextlib
 import os
 
 import numpy as np
@@ -87,6 +88,43 @@ class Guarded:
     def untouched(self, name):
         buf, n = self.bufs[name]
         return bool((buf == CANARY).all())
+
+
+class LaunchRecord:
+    """What record_launches() saw, in launch order: `launches` holds one [name, nbytes, flops, whats] per _hip.launch call (whats: the
+    `what` strings _hip.check was handed while that launch ran), `names` just the names."""
+
+    def __init__(self):
+        self.launches, self.names = [], []
+
+
+@contextlib.contextmanager
+def record_launches():
+    """Record every launch through _hip.launch while the block runs; the launches themselves run as usual (timers included).  The
+    previous _hip.launch / _hip.check come back on exit."""
+    from meta_interpolation_amd import _hip
+    rec, launch, check, running = LaunchRecord(), _hip.launch, _hip.check, []
+
+    def spy_launch(name, fn, nbytes=0, flops=0):
+        entry = [name, nbytes, flops, []]
+        rec.launches.append(entry)
+        rec.names.append(name)
+        running.append(entry)
+        try:
+            return launch(name, fn, nbytes=nbytes, flops=flops)
+        finally:
+            running.pop()
+
+    def spy_check(code, what):
+        if running:
+            running[-1][3].append(what)
+        return check(code, what)
+
+    _hip.launch, _hip.check = spy_launch, spy_check
+    try:
+        yield rec
+    finally:
+        _hip.launch, _hip.check = launch, check
 
 
 def build_system(model, overrides, fuse=1, device="cuda"):

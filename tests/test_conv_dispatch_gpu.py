@@ -13,8 +13,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from meta_interpolation_amd import _hip, hip_ops
+from meta_interpolation_amd import hip_ops
 from tests import conv_ref as R
+from tests.helpers import record_launches
 from tests import test_conv_layers_gpu as L
 from tests import test_conv_variants_gpu as V
 
@@ -110,25 +111,24 @@ def _run(name):
     xr = x.clone().requires_grad_(c["need_x"])
     wr = (w if T else w[0]).clone().requires_grad_()
     br = None if b is None else (b if T else b[0]).clone().requires_grad_()
-    names, orig = [], _hip.launch
-    _hip.launch = lambda n, fn, **k: (names.append(n), orig(n, fn, **k))[1]
     hip_ops.set_weight_gradient_overlap(c["overlap"])
     try:
-        if T:
-            y = hip_ops.conv_bias_act_tasks(xr, wr, br, c["stride"], c["pad"], 1, c["slope"], direct=c["direct"], in_slope=c["in_slope"],
-                                            defer=c["defer"], out_unit16=c["out_unit16"])
-        else:
-            y = hip_ops.conv_bias_act(xr, wr, br, c["stride"], c["pad"], 1, 1, c["slope"], direct=c["direct"], reflect=c["reflect"],
-                                      in_slope=c["in_slope"], defer=c["defer"])
-        n_fwd = len(names)
-        gy = torch.randn(y.shape, device=DEV, generator=g)
-        inputs = ([xr] if c["need_x"] else []) + [wr] + ([br] if br is not None else [])
-        grads = list(torch.autograd.grad(y, inputs, gy))
-        hip_ops.join_weight_gradients()
-        torch.cuda.synchronize()
+        with record_launches() as rec:
+            names = rec.names
+            if T:
+                y = hip_ops.conv_bias_act_tasks(xr, wr, br, c["stride"], c["pad"], 1, c["slope"], direct=c["direct"], in_slope=c["in_slope"],
+                                                defer=c["defer"], out_unit16=c["out_unit16"])
+            else:
+                y = hip_ops.conv_bias_act(xr, wr, br, c["stride"], c["pad"], 1, 1, c["slope"], direct=c["direct"], reflect=c["reflect"],
+                                          in_slope=c["in_slope"], defer=c["defer"])
+            n_fwd = len(names)
+            gy = torch.randn(y.shape, device=DEV, generator=g)
+            inputs = ([xr] if c["need_x"] else []) + [wr] + ([br] if br is not None else [])
+            grads = list(torch.autograd.grad(y, inputs, gy))
+            hip_ops.join_weight_gradients()
+            torch.cuda.synchronize()
     finally:
         hip_ops.set_weight_gradient_overlap(False)
-        _hip.launch = orig
     y = y.detach()
     if c["out_unit16"]:         # the memory is [N][Ho][Wo/16][Co][16] under the shape [N,Co,Ho,Wo]
         Ho, Wo = y.shape[2:]

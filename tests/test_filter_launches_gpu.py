@@ -9,12 +9,15 @@ The file is written to pass unchanged on both trees.
 The layers are the smallest that reach each kind of filter ('convk': packed for the direct kernel, 'wino2': the F(2x2) transform), shared
 weights and a per-task (T = 2) copy.  Every pass compares y and gx with float64 conv2d through the local gate of tests/conv_ref.py with
 the family constants of test_conv_dispatch_gpu.py -- in particular a pass after the weight changed must follow the new weight."""
+import contextlib
+
 import pytest
 import torch
 
 from meta_interpolation_amd import _hip, hip_ops, model_utils
 from tests import conv_ref as R
 from tests import test_conv_dispatch_gpu as D
+from tests.helpers import record_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -65,16 +68,11 @@ EXPECTED = {
 }
 
 
-class _Record:
+@contextlib.contextmanager
+def _Record():
     """The names of every launch through _hip.launch while the block runs."""
-
-    def __enter__(self):
-        self.names, self.orig = [], _hip.launch
-        _hip.launch = lambda n, fn, **k: (self.names.append(n), self.orig(n, fn, **k))[1]
-        return self.names
-
-    def __exit__(self, *exc):
-        _hip.launch = self.orig
+    with record_launches() as rec:
+        yield rec.names
 
 
 def _reset():
@@ -98,9 +96,7 @@ def _tensors(seed):
 def _pass(name, x, w, b, gy, cache=None, backward=True):
     """One forward (and backward) of the layer on the GPU, y and gx held to float64; returns the gradients of (w, b) where they ask."""
     T, N, Ci, Co, H, W, K, pad = LAYERS[name]
-    names, orig = [], _hip.launch
-    _hip.launch = lambda n, fn, **k: (names.append(n), orig(n, fn, **k))[1]
-    try:
+    with _Record() as names:
         xr = x.clone().requires_grad_(backward)
         if T is None:
             y = hip_ops.conv_bias_act(xr, w, b, 1, pad, 1, 1, SLOPE, False, cache)
@@ -112,8 +108,6 @@ def _pass(name, x, w, b, gy, cache=None, backward=True):
             inputs = [xr] + [t for t in (w, b) if t.requires_grad]
             grads = torch.autograd.grad(y, inputs, gy)
         torch.cuda.synchronize()
-    finally:
-        _hip.launch = orig
     w5 = (w if T else w[None]).detach().cpu()
     b2 = (b if T else b[None]).detach().cpu()
     ref, mag = R.conv_tasks64(x.cpu(), w5, pad, T or 1, bias=b2)
