@@ -83,7 +83,8 @@ extern "C" {
  * SSIM, savfi_msssim_scratch_bytes, savfi_msssim_f32, savfi_msssim_bwd_f32; then, for SepConv's second-order terms,
  * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form; then, for the Laplacian-pyramid loss term, savfi_laploss_scratch_bytes,
  * savfi_laploss_f32, savfi_laploss_bwd_f32; then, for the census loss term, savfi_census_scratch_bytes, savfi_census_f32,
- * savfi_census_bwd_f32; then, for the second-order terms of the two warps, savfi_voxelwarp_bwd2_f32, savfi_flowwarp_bwd2_f32. */
+ * savfi_census_bwd_f32; then, for the second-order terms of the two warps, savfi_voxelwarp_bwd2_f32, savfi_flowwarp_bwd2_f32; then, with
+ * the one SepConv route, savfi_sepconv_route, savfi_sepconv_debug_span_bytes. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -134,8 +135,10 @@ int savfi_sepconv_bwd2_f32(const float* in, const float* v, const float* h, cons
  * a [B * 4, K, Ho, Wo] tensor (sample 4 b + s = sub-network s) that the two local convolutions read -- and their filter gradients write --
  * in place with tap_bstride = 4 * K.  K = 51, C = 3, Wo % 4 == 0, every tensor below 2^31 bytes; SAVFI_E_UNSUPPORTED otherwise (the
  * caller copies the slices and uses the contiguous entry points).  No gI (frames carry no gradient on this path). */
-/* 1 when the strided / frames8 / pair entry points take the problem in this process (shapes, sizes AND the A/B environment switches that
- * make them return SAVFI_E_UNSUPPORTED), 0 otherwise: what a caller asks before it chooses the interleaved tap tensor. */
+/* 1 when the strided / frames8 / pair entry points take the problem in this library (shapes, sizes AND the switches of a variant build
+ * that make them return SAVFI_E_UNSUPPORTED), 0 otherwise: what a caller asks before it chooses the interleaved tap tensor.  They take
+ * what savfi_sepconv_route (below) sends to the wave-specialised kernels for want = 3 in ONE launch (chunk == B), with the strided tap
+ * buffer inside the span too; they do not cut a batch into chunks. */
 int savfi_sepconv_taps_strided_supported(int B, int C, int Ho, int Wo, int K, int tap_bstride);
 int savfi_sepconv_fwd_taps_strided_f32(const float* in, const float* v, const float* h, float* out, int B, int C, int Ho, int Wo, int K,
                                        int tap_bstride, void* stream);
@@ -211,11 +214,30 @@ int savfi_sepconv_ws_debug_spin_limit(int limit, int* previous);
 #define SAVFI_SEPCONV_PARTITION_X6   1
 #define SAVFI_SEPCONV_PARTITION_FP32 2
 int savfi_sepconv_partition(int kind, int B, int Ho, int Wo, int cus, int block, int* g0, int* g1);
+/* The route of savfi_sepconv_fwd_f32 / savfi_sepconv_bwd_f32: which kernel a call runs, and on how many consecutive samples per launch.
+ *   want   0 = forward, 1 = gV only, 2 = gH only, 3 = gV and gH (gI is always one direct launch over the whole batch)
+ *   chunk  the largest Bc <= B for which both Bc * 51 * Ho * Wo * 4 and Bc * 3 * (Ho + 50) * (Wo + 50) * 4 are below the span of 2^31
+ *          bytes (the persistent kernels address each tensor through one buffer descriptor); 0 if not even one sample fits
+ *   K == 51, C == 3 and chunk > 0:  want 0 or 3 -> SAVFI_SEPCONV_PARTITION_WS if Wo % 4 == 0, else SAVFI_SEPCONV_PARTITION_X6
+ *                                   want 1 or 2 -> SAVFI_SEPCONV_PARTITION_FP32
+ *   anything else:                  SAVFI_SEPCONV_ROUTE_DIRECT (one thread per output element), reported with chunk = B
+ * With chunk < B the entry point launches the kernel once per run of `chunk` consecutive samples (the last run shorter): ordinary
+ * launches on the caller's stream, capturable; every sample's bits are those of a call with that sample alone.
+ * Variant builds: -DSAVFI_SEPCONV_NO_MFMA always DIRECT; _NO_WS: X6 where WS stands above (_NO_WS_FWD: for want == 0 only); _F32_MFMA:
+ * FP32 for every want != 0.
+ * Returns the kernel, or SAVFI_E_SHAPE (want outside 0..3, a dimension <= 0) / SAVFI_E_TOOBIG (the limits of savfi_sepconv_fwd_f32);
+ * *chunk (may be NULL) receives the chunk.  Needs no device.  savfi_sepconv_partition answers SAVFI_E_TOOBIG exactly where chunk < B. */
+#define SAVFI_SEPCONV_ROUTE_DIRECT 3
+int savfi_sepconv_route(int want, int B, int C, int Ho, int Wo, int K, int* chunk);
 /* Test hook: the CU count that the launches of those kernels plan for.  0 restores the device's count; other values are clamped to
  * [1, device count].  Host side only -- fewer workgroups that take more phases each is an ordinary launch (there is no dependency
  * between workgroups) -- so tests/ can drive every state of the partition on any device.  *previous (may be NULL) receives the old
  * setting (0 = the device's count); launches issued afterwards use the new one. */
 int savfi_sepconv_debug_cus(int cus, int* previous);
+/* Test hook: the span (bytes) that the route above holds the tensors of one persistent launch below.  0 restores 2^31; other values are
+ * clamped to [1, 2^31].  Host state only -- a smaller span means more, smaller launches; nothing in a kernel reads it -- so tests/ can
+ * drive the chunk loop on small tensors.  *previous (may be NULL) receives the old span; calls issued afterwards use the new one. */
+int savfi_sepconv_debug_span_bytes(int64_t bytes, int64_t* previous);
 
 /* ------------------------------------------------------------------------------------
  * VoxelFlow warp + blend (syn_type 'inter').

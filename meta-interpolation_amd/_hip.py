@@ -18,6 +18,7 @@ RULE_SGD, RULE_ADAM, RULE_ADAMAX_LSLR, RULE_ADAMAX_MSGD = 0, 1, 2, 3
 LR_SCALAR, LR_ELEMENT = 0, 1
 SSIM_RANGE_PER_ROW, SSIM_RANGE_BATCH, SSIM_RANGE_FIXED = 0, 1, 2
 SEPCONV_PARTITION_WS, SEPCONV_PARTITION_X6, SEPCONV_PARTITION_FP32 = 0, 1, 2
+SEPCONV_ROUTE_DIRECT = 3                  # savfi_sepconv_route: the direct kernels (the three above: the persistent ones)
 ABI_VERSION = 24
 
 _ERRORS = {-1: "SAVFI_E_NULL (a required pointer is NULL)",
@@ -55,6 +56,8 @@ _PROTOTYPES = {
     "savfi_sepconv_ws_debug_spin_limit": [c_int, POINTER(c_int)],
     "savfi_sepconv_partition": [c_int] * 6 + [POINTER(c_int), POINTER(c_int)],
     "savfi_sepconv_debug_cus": [c_int, POINTER(c_int)],
+    "savfi_sepconv_route": [c_int] * 6 + [POINTER(c_int)],
+    "savfi_sepconv_debug_span_bytes": [c_int64, _I64P],
     "savfi_conv3x3_dgrad_masked_f32": [_P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_convk_dgrad_masked_f32": [_P, _P, _P, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_voxelwarp_fwd_f32": [_P, _P, _P, c_int, c_int, c_int, _P],

@@ -396,7 +396,7 @@ constexpr size_t mfma_lds_bytes(int rows) {
 }
 
 // rows per workgroup (one workgroup per CU: the window fills most of its LDS): as few rounds of the 256 CUs as possible, each costing
-// its rows plus the staging of the 50-row halo (csrc/sepconv.hip mfma_rows; the row here is ~3x as long, the halo counts for less)
+// its rows plus the staging of the 50-row halo (the rule of the tiled first-order kernels that HISTORY.md records; the row here is ~3x as long, the halo counts for less)
 int bwd2_rows(int B, int Ho, int Wo) {
   int best = 8;
   long best_cost = -1;

@@ -6,7 +6,10 @@ runs that start inside a strip, stretches across sample boundaries, long runs, r
 transcription.  Here the library's own answer (savfi_sepconv_partition: the host code the launches size their grids with, the
 __host__ __device__ functions the kernels cut their pieces with) is compared with it over a seeded sweep of (B, Ho, Wo, cus), so a change
 of WS_RUN_COST, XPR, XMC, MC or of a per_wg formula in C that the transcription does not follow fails here, on a machine without a GPU.
-The properties a partition must have whatever its formula are asserted on the library's pieces."""
+The properties a partition must have whatever its formula are asserted on the library's pieces.
+
+The route of the contiguous entry points (savfi_sepconv_route: which of those kernels, or the direct ones, a call runs, and in chunks of
+how many samples) is held to its table here as well, with the span hook that the GPU cases cut their batches by."""
 import ctypes
 import math
 import random
@@ -148,3 +151,120 @@ def test_float64_reference_agrees_with_autograd_through_the_oracle():
         ref.backward(gO.double())
         for a, b in ((out, ref.detach()), (gV, v64.grad), (gH, h64.grad)):
             assert (a - b).abs().max().item() <= 1e-13 * b.abs().max().item()
+
+
+# ---- the route of the contiguous entry points (savfi_sepconv_route) and the span it cuts a batch by ------------------------------------
+DIRECT = _hip.SEPCONV_ROUTE_DIRECT
+SPAN = 1 << 31
+ANY, FWD_BOTH, ONE = (0, 1, 2, 3), (0, 3), (1, 2)
+# (wants, B, C, Ho, Wo, K) -> (kernel, chunk) or a negative error: the default build
+ROUTES = [
+    (FWD_BOTH, 8, 3, 256, 448, 51, (R.WS, 8)),
+    (FWD_BOTH, 8, 3, 256, 450, 51, (R.X6, 8)),
+    (ONE, 8, 3, 256, 448, 51, (R.FP32, 8)),
+    (ONE, 8, 3, 256, 450, 51, (R.FP32, 8)),
+    (ANY, 2, 3, 64, 64, 5, (DIRECT, 2)),
+    (ANY, 2, 1, 64, 64, 51, (DIRECT, 2)),
+    (FWD_BOTH, 8, 3, 1080, 1920, 51, (R.WS, 5)),          # 5 x 423 014 400 bytes of taps are below 2^31, 6 x are not
+    ((1,), 8, 3, 1080, 1920, 51, (R.FP32, 5)),
+    (ANY, 1, 3, 3000, 3600, 51, (DIRECT, 1)),             # one sample's taps exceed 2^31 bytes
+    (ANY, 1, 3, 1, 5000000, 51, (DIRECT, 1)),             # the taps fit, the input window does not
+    (ANY, 0, 3, 8, 8, 51, -2),
+    (ANY, 1286, 3, 8, 8, 51, -4),                         # B K > 65535
+]
+
+
+def _route(want, B, C, Ho, Wo, K):
+    """(kernel, chunk) of the library, or its negative error"""
+    chunk = ctypes.c_int(-7)
+    kernel = _hip.lib().savfi_sepconv_route(want, B, C, Ho, Wo, K, ctypes.byref(chunk))
+    assert _hip.lib().savfi_sepconv_route(want, B, C, Ho, Wo, K, None) == kernel       # chunk may be NULL
+    return kernel if kernel < 0 else (kernel, chunk.value)
+
+
+def _sample_bytes(Ho, Wo):
+    """what one sample adds to the larger of a launch's tap tensor and its input-window tensor"""
+    return max(R.K * Ho * Wo * 4, 3 * (Ho + R.K - 1) * (Wo + R.K - 1) * 4)
+
+
+@pytest.fixture
+def span():
+    """span(L): the persistent kernels' tensors must stay below L bytes from now on (0: 2^31); restored when the test ends"""
+    lib = _hip.lib()
+    try:
+        yield lambda L: _hip.check(lib.savfi_sepconv_debug_span_bytes(int(L), None), "savfi_sepconv_debug_span_bytes")
+    finally:
+        lib.savfi_sepconv_debug_span_bytes(0, None)
+
+
+def test_route_table():
+    assert (R.WS, R.X6, R.FP32, DIRECT) == (0, 1, 2, 3)
+    for wants, B, C, Ho, Wo, K, expected in ROUTES:
+        for want in wants:
+            assert _route(want, B, C, Ho, Wo, K) == expected, (want, B, C, Ho, Wo, K)
+    assert _route(4, 8, 3, 256, 448, 51) == -2 and _route(-1, 8, 3, 256, 448, 51) == -2
+
+
+def test_partition_refuses_exactly_what_the_route_cuts_into_chunks():
+    g0, g1 = ctypes.c_int(), ctypes.c_int()
+    lib = _hip.lib()
+    shapes = [(B, Ho, Wo) for _, B, C, Ho, Wo, K, e in ROUTES if (C, K) == (3, 51) and not isinstance(e, int)]
+    shapes += [(5, 1080, 1920), (6, 1080, 1920), (64, 2048, 2048), (2, 3000, 3600)] + [c[:3] for c in FIXED]
+    seen = set()
+    for B, Ho, Wo in shapes:
+        for want in ANY:
+            kernel, chunk = _route(want, B, 3, Ho, Wo, 51)
+            kind = kernel if kernel != DIRECT else (R.WS if Wo % 4 == 0 else R.X6)       # DIRECT here: not even one sample fits
+            got = lib.savfi_sepconv_partition(kind, B, Ho, Wo, 256, 0, ctypes.byref(g0), ctypes.byref(g1))
+            whole = kernel != DIRECT and chunk == B
+            assert (got == -4) == (not whole) and (got > 0) == whole, (want, B, Ho, Wo, kernel, chunk, got)
+            seen.add(whole)
+    assert seen == {True, False}
+    assert lib.savfi_sepconv_partition(3, 1, 8, 8, 4, 0, ctypes.byref(g0), ctypes.byref(g1)) == -3          # DIRECT has no partition
+
+
+def test_span_hook_sets_the_chunk(span):
+    lib = _hip.lib()
+    prev = ctypes.c_int64(-7)
+    P = ctypes.byref
+    assert lib.savfi_sepconv_debug_span_bytes(0, P(prev)) == 0 and prev.value == SPAN            # nothing has set it
+    assert lib.savfi_sepconv_debug_span_bytes(12345, P(prev)) == 0 and prev.value == SPAN
+    assert lib.savfi_sepconv_debug_span_bytes(-3, P(prev)) == 0 and prev.value == 12345           # clamped to 1
+    assert lib.savfi_sepconv_debug_span_bytes(1 << 40, P(prev)) == 0 and prev.value == 1          # clamped to 2^31
+    assert lib.savfi_sepconv_debug_span_bytes(0, P(prev)) == 0 and prev.value == SPAN
+    assert lib.savfi_sepconv_debug_span_bytes(0, P(prev)) == 0 and prev.value == SPAN
+    for B, Ho, Wo in [(3, 10, 36), (3, 10, 35), (3, 5, 70), (8, 256, 448), (7, 1, 300), (5, 37, 45)]:
+        m = _sample_bytes(Ho, Wo)
+        for L in (1, m - 1, m, m + 1, 2 * m, 2 * m + 1, 3 * m, 3 * m + 1, B * m, B * m + 1, SPAN):
+            span(L)
+            want_chunk = min(B, (L - 1) // m)                 # the largest Bc with Bc m < L
+            assert want_chunk * m < L and (want_chunk == B or (want_chunk + 1) * m >= L)
+            for want in ANY:
+                kernel = R.FP32 if want in ONE else (R.WS if Wo % 4 == 0 else R.X6)
+                assert _route(want, B, 3, Ho, Wo, 51) == ((kernel, want_chunk) if want_chunk else (DIRECT, B)), (B, Ho, Wo, L, want)
+            # the strided entry points do not cut: they take the problem only whole
+            assert lib.savfi_sepconv_taps_strided_supported(B, 3, Ho, Wo, 51, 51) == int(Wo % 4 == 0 and want_chunk == B)
+    span(0)
+    assert _route(0, 8, 3, 256, 448, 51) == (R.WS, 8)
+
+
+def _strided_supported_by_rule(B, C, Ho, Wo, K, tb):
+    """the rule the strided / frames8 / pair entry points have had since they exist (default build)"""
+    if (K, C) != (51, 3) or Wo % 4 or tb < K or B * K > 65535 or Ho + K - 1 > 65535:
+        return 0
+    return int(((B - 1) * tb + K) * Ho * Wo * 4 < SPAN and B * _sample_bytes(Ho, Wo) < SPAN)
+
+
+def test_taps_strided_supported_keeps_its_answers():
+    lib = _hip.lib()
+    shapes = [c[:3] for c in FIXED]
+    shapes += [(1, 16, 32), (2, 37, 36), (1, 128, 128), (2, 64, 96), (1, 9, 68), (3, 5, 4), (2, 37, 48), (3, 5, 16), (2, 40, 64),
+               (3, 40, 64), (1, 24, 48), (2, 33, 32)]                                  # tests/test_sepconv_frames8_gpu.py
+    shapes += [(8, 1080, 1920), (5, 1080, 1920), (2, 1080, 1920), (1, 3000, 3600), (10, 256, 448), (11, 256, 448)]
+    answers = set()
+    for B, Ho, Wo in shapes:
+        for C, K, tb in ((3, 51, 51), (3, 51, 204), (3, 51, 50), (1, 51, 51), (3, 5, 5), (3, 5, 204)):
+            got = lib.savfi_sepconv_taps_strided_supported(B, C, Ho, Wo, K, tb)
+            assert got == _strided_supported_by_rule(B, C, Ho, Wo, K, tb), (B, C, Ho, Wo, K, tb)
+            answers.add(((C, K, tb), got))
+    assert ((3, 51, 51), 1) in answers and ((3, 51, 51), 0) in answers and ((3, 51, 204), 1) in answers and ((3, 51, 204), 0) in answers

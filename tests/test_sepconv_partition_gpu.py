@@ -33,6 +33,13 @@ was bit-identical at the two counts.  The gate of 1e-5 is 15 to 40 times what th
     x6                          1.81e-07   2.77e-07   2.64e-07
     fp32 persistent gV only     -          6.43e-07   -
     fp32 persistent gH only     -          -          6.37e-07
+
+The chunk loop of the contiguous entry points (a batch beyond the span of one buffer descriptor runs in chunks of consecutive samples;
+test_batch_chunks_equal_the_samples_one_by_one, B = 3, chunks of 2 + 1 and 1 + 1 + 1: bit-identical to the samples one by one), and the
+direct kernels the same calls run when not even one sample fits the span:
+    ws 10x36, chunked           8.15e-08   1.89e-07   1.51e-07        direct    2.12e-07   2.06e-07   2.25e-07
+    x6 10x35, chunked           1.34e-07   1.69e-07   1.80e-07        direct    1.68e-07   2.15e-07   2.33e-07
+    fp32 5x70, chunked          -          4.13e-07   3.76e-07        direct    -          1.95e-07   2.29e-07
 """
 import ctypes
 import functools
@@ -400,3 +407,86 @@ def test_fp32_persistent_kernel_across_the_partition(case, claims, plan_for):
         for planned in (cus, 0):
             _record(name, case, planned or _device_cus(), got[planned][name], ref)
         _assert_same_bits(got[cus][name], got[0][name], "%s %s" % (name, case))
+
+
+# ---- the chunk loop of the contiguous entry points ---------------------------------------------------------------------------------------
+# A batch whose tensors do not fit the span of one buffer descriptor (2^31 bytes) is launched in runs of `chunk` consecutive samples
+# (savfi_sepconv_route).  savfi_sepconv_debug_span_bytes shrinks the span -- host state only -- so that B = 3 samples of the smallest
+# shapes that are ragged in both directions for each kernel are cut 2 + 1 and 1 + 1 + 1; with the span at one sample's size nothing
+# fits and the direct kernels run.  (kernel, B, Ho, Wo, the wants the case calls: 0 forward, 3 gV and gH, 1 gV only, 2 gH only)
+CHUNK_CASES = [
+    ("ws", R.WS, (3, 10, 36), (0, 3)),                    # phases of 4 rows, strips of 32 columns; the taps are the larger tensor
+    ("x6", R.X6, (3, 10, 35), (0, 3)),
+    ("fp32", R.FP32, (3, 5, 70), (1, 2)),                 # phases of 2 rows, strips of 64 columns; the input window is the larger tensor
+]
+
+
+@pytest.fixture
+def span():
+    """span(L): the persistent kernels' tensors must stay below L bytes from now on (0: 2^31); restored when the test ends"""
+    lib = _hip.lib()
+    try:
+        yield lambda L: _hip.check(lib.savfi_sepconv_debug_span_bytes(int(L), None), "savfi_sepconv_debug_span_bytes")
+    finally:
+        lib.savfi_sepconv_debug_span_bytes(0, None)
+
+
+def _routes(wants, B, Ho, Wo):
+    """{(kernel, chunk)} of the library's route over `wants`"""
+    chunk, got = ctypes.c_int(-1), set()
+    for want in wants:
+        kernel = _hip.lib().savfi_sepconv_route(want, B, 3, Ho, Wo, K, ctypes.byref(chunk))
+        got.add((kernel, chunk.value))
+    return got
+
+
+def _contiguous_launches(f0, v, h, gO, wants):
+    """savfi_sepconv_fwd_f32 / savfi_sepconv_bwd_f32 for every want of the case: (out, gV, gH), None = not asked for"""
+    lib, st = _hip.lib(), _hip.current_stream()
+    B, _, Ho, Wo = gO.shape
+    dims = (B, 3, Ho, Wo, K)
+    bufs = _Buffers()
+    out = gV = gH = None
+    if 0 in wants:
+        out = bufs.new(B, 3, Ho, Wo)
+        _hip.check(lib.savfi_sepconv_fwd_f32(P(f0), P(v), P(h), P(out), *dims, st), "fwd")
+    if 3 in wants:
+        gV, gH = bufs.new(B, K, Ho, Wo), bufs.new(B, K, Ho, Wo)
+        _hip.check(lib.savfi_sepconv_bwd_f32(P(f0), P(v), P(h), P(gO), None, P(gV), P(gH), *dims, st), "bwd")
+    if 1 in wants:
+        gV = bufs.new(B, K, Ho, Wo)
+        _hip.check(lib.savfi_sepconv_bwd_f32(P(f0), P(v), P(h), P(gO), None, P(gV), None, *dims, st), "gV only")
+    if 2 in wants:
+        gH = bufs.new(B, K, Ho, Wo)
+        _hip.check(lib.savfi_sepconv_bwd_f32(P(f0), P(v), P(h), P(gO), None, None, P(gH), *dims, st), "gH only")
+    bufs.check()
+    if lib.savfi_sepconv_ws_errors() != 0:
+        raise AssertionError("a bounded wait of the wave-specialised kernels gave up")
+    return out, gV, gH
+
+
+@pytest.mark.parametrize("name,kind,shape,wants", CHUNK_CASES, ids=[c[0] for c in CHUNK_CASES])
+def test_batch_chunks_equal_the_samples_one_by_one(name, kind, shape, wants, span):
+    B, Ho, Wo = shape
+    m = max(K * Ho * Wo * 4, 3 * (Ho + K - 1) * (Wo + K - 1) * 4)          # one sample of the larger of the tap and the window tensor
+    f0, _, taps, gO = (t.to(DEV) for t in _problem(B, Ho, Wo))
+    t5 = taps.view(B, 4, K, Ho, Wo)
+    v, h = t5[:, 0].contiguous(), t5[:, 1].contiguous()
+    ref = _reference(B, Ho, Wo, 0)
+
+    span(0)                                               # the samples one by one, nothing cut
+    assert _routes(wants, 1, Ho, Wo) == {(kind, 1)} and _routes(wants, B, Ho, Wo) == {(kind, B)}
+    singles = [_contiguous_launches(f0[b:b + 1], v[b:b + 1], h[b:b + 1], gO[b:b + 1], wants) for b in range(B)]
+    one_by_one = [None if xs[0] is None else torch.cat(xs) for xs in zip(*singles)]
+
+    for L, chunk in ((3 * m, 2), (m + 1, 1)):             # launches of 2 + 1 samples, of 1 + 1 + 1
+        span(L)
+        assert _routes(wants, B, Ho, Wo) == {(kind, chunk)}, "the span hook did not take"
+        got = _contiguous_launches(f0, v, h, gO, wants)
+        _record("%s chunks of %d" % (name, chunk), shape, _device_cus(), got, ref)
+        _assert_same_bits(one_by_one, got, "%s %s in chunks of %d against its samples one by one" % (name, shape, chunk))
+
+    span(m)                                               # not even one sample fits: the direct kernels
+    assert _routes(wants, B, Ho, Wo) == {(_hip.SEPCONV_ROUTE_DIRECT, B)}
+    got = _contiguous_launches(f0, v, h, gO, wants)
+    _record("%s span of one sample: direct" % name, shape, _device_cus(), got, ref)

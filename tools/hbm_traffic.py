@@ -20,17 +20,6 @@ CASES = [(1, 384, 512), (1, 256, 448), (2, 256, 448), (4, 256, 448), (8, 256, 44
 PAIR_CASES = [(4, 256, 448), (8, 256, 448)]
 
 
-def mfma_rows(B, Ho, Wo):
-    """csrc/sepconv.hip mfma_rows(): rows per workgroup of the MFMA kernels."""
-    best, best_cost = 12, None
-    for r in (12, 8, 16):
-        wgs = B * -(-Wo // 64) * -(-Ho // r)
-        cost = -(-wgs // 256) * (r + 2)
-        if best_cost is None or cost < best_cost:
-            best, best_cost = r, cost
-    return best
-
-
 def run():
     import torch
     from meta_interpolation_amd import _hip
