@@ -50,26 +50,6 @@ __device__ __forceinline__ float census_a(float ds, float dh) {
   return (0.162f * diff) / ((e * e) * (s * sqrtf(s)));
 }
 
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, SAVFI_WAVE);
-  return x;
-}
-
-// block-wide sum, valid in thread 0; always the same order
-__device__ __forceinline__ double block_sum_d(double x, double* lds /* NW */) {
-  x = wave_sum_d(x);
-  if ((threadIdx.x & (SAVFI_WAVE - 1)) == 0) lds[threadIdx.x / SAVFI_WAVE] = x;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += lds[w];
-  }
-  __syncthreads();
-  return t;
-}
-
 // The gray patches of sample z around tile (y0, x0) -> LDS, entry (r, c) = pixel (y0 - 3 + r, x0 - 3 + c), zero outside the frame.
 template <int C>
 __device__ __forceinline__ void stage(const float* __restrict__ sr, const float* __restrict__ hr, float* __restrict__ ps,
@@ -124,7 +104,7 @@ __global__ __launch_bounds__(NT) void census_tiles(const float* __restrict__ sr,
       }
     }
   }
-  const double tot = block_sum_d(sum, red);
+  const double tot = block_sum_d<NW>(sum, red);
   if (threadIdx.x == 0) partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -135,7 +115,7 @@ __global__ __launch_bounds__(NT) void census_finish(const double* __restrict__ p
   const double* p = partial + (size_t)blockIdx.x * count;
   double a = 0.0;
   for (int64_t i = threadIdx.x; i < count; i += NT) a += p[i];
-  const double tot = block_sum_d(a, red);
+  const double tot = block_sum_d<NW>(a, red);
   if (threadIdx.x == 0) result[blockIdx.x] = (float)(tot * inv);
 }
 

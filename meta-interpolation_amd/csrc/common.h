@@ -49,6 +49,34 @@ __device__ __forceinline__ float block_sum(float x, float* lds /* >= NW floats *
   return t;
 }
 
+// The same two in double.  block_sum_d: thread 0 adds the waves' sums lds[0 .. NW - 1] in that order; valid in thread 0.
+__device__ __forceinline__ double wave_sum_d(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, SAVFI_WAVE);
+  return x;
+}
+
+template <int NW>
+__device__ __forceinline__ double block_sum_d(double x, double* lds /* >= NW doubles */) {
+  x = wave_sum_d(x);
+  if ((threadIdx.x & (SAVFI_WAVE - 1)) == 0) lds[threadIdx.x / SAVFI_WAVE] = x;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t += lds[w];
+  }
+  __syncthreads();
+  return t;
+}
+
+// 64-lane butterfly max; every lane ends with it.
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, SAVFI_WAVE));
+  return x;
+}
+
 // utils.quantize(img, 1.) of a unit-range value: img.mul(255).clamp(0, 255).round() -- one fp32 multiply, a clamp that lets NaN
 // through as torch.clamp does (fminf / fmaxf would drop it; +-inf go to 255 / 0), ties to even.  The integers of the PSNR / SSIM
 // metric (csrc/ssim.hip) and the bytes of a written frame (csrc/frames.hip) both come from here.

@@ -71,26 +71,6 @@ __device__ __forceinline__ float adj_w(int o, int y, int n) {
   return w;
 }
 
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, SAVFI_WAVE);
-  return x;
-}
-
-// block-wide sum, valid in thread 0; always the same order
-__device__ __forceinline__ double block_sum_d(double x, double* lds /* NW */) {
-  x = wave_sum_d(x);
-  if ((threadIdx.x & (SAVFI_WAVE - 1)) == 0) lds[threadIdx.x / SAVFI_WAVE] = x;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += lds[w];
-  }
-  __syncthreads();
-  return t;
-}
-
 // Zero-inserted map around a tile -> LDS [ROWS][STRIDE], entry (r, c) = position (oy + r, ox + c) of the H x W level, reflected.
 // `coarse(i, j)` returns c_{s+1}[i][j] for 0 <= i < ceil(H / 2), 0 <= j < ceil(W / 2).
 template <int ROWS, int STRIDE, typename F>
@@ -178,7 +158,7 @@ __global__ __launch_bounds__(NT) void lap_level(const float* __restrict__ a, con
     const float bv = band(fp[(r + 4) * FPS + c + 4], tap5(p[0], p[T], p[2 * T], p[3 * T], p[4 * T]));
     if (y0 + r < H && x0 + c < W) sum += (double)fabsf(bv);
   }
-  const double tot = block_sum_d(sum, red);
+  const double tot = block_sum_d<NW>(sum, red);
   if (threadIdx.x == 0) partial[((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -208,7 +188,7 @@ __global__ __launch_bounds__(NT) void lap_finish(const void* __restrict__ scratc
   double a = 0.0;
   for (int i = threadIdx.x; i < f.last_n; i += NT) a += (double)fabsf(c[i]);
   acc += scale * a;
-  const double tot = block_sum_d(acc, red);
+  const double tot = block_sum_d<NW>(acc, red);
   if (threadIdx.x == 0) result[row] = (float)(tot * f.inv_n0);
 }
 

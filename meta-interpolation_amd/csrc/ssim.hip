@@ -6,26 +6,29 @@
 //
 // Here: `rows` independent losses per launch (one per sample: tasks in lockstep, the two support triplets of a step).
 //   ssim_range   max / min of every row of the prediction -> per-block partial extrema (skipped for a fixed L)
-//   ssim_fwd     a workgroup owns a 16 x 64 tile of SSIM values of one channel plane: 26 x 76 patches of both images into LDS
-//                (float4 where the operands allow), 11-tap row pass over the five products into LDS, column pass out of LDS
+//   ssim_fwd     fwd_tile: a workgroup owns a 16 x 64 tile of SSIM values of one channel plane: 26 x 76 patches of both images into
+//                LDS (float4 where the operands allow), 11-tap row pass over the five products into LDS, column pass out of LDS
 //                (separable: 22 instead of 121 multiply-adds per moment), map, one partial sum per workgroup.  It reduces
 //                the row's partial extrema itself (no host read: the op is capturable) and publishes the row's range word.
 //   ssim_finish  adds a row's partial sums in a fixed order (no float atomics: bit-reproducible) -> (1 - sum / n) / 2
-//   ssim_bwd     one launch: a workgroup owns 16 x 32 pixels of d loss / d sr, recomputes the moments on the tile grown by
+//   ssim_bwd     bwd_tile, one launch: a workgroup owns 16 x 32 pixels of d loss / d sr, recomputes the moments on the tile grown by
 //                the 10-pixel halo (26 x 42 SSIM positions from 36 x 56 patches), forms the three coefficient planes a, b, c in
 //                LDS and applies the adjoint window (row pass, column pass) to them:
 //                  d loss / d sr = -(g / (2 n)) (G^T[a] + 2 sr G^T[b] + hr G^T[c])
 //                  b = d map / d s1, c = d map / d s12, a = (d map / d mu1 at fixed s1, s12) - 2 mu1 b - mu2 c
 //                Nothing is kept from the forward but the two images and the range word.
-// The PSNR / SSIM evaluation metric (utils.py:171-204: quantize + calc_psnr + ssim(val_range=255)) is the forward tile once more:
-//   metric_tile    fwd_tile<METRIC>: both unit-range images quantised to 0 .. 255 as they are loaded into LDS, L = 255 fixed (no range
-//                  pass, no range word), and next to the SSIM partial sum the integer sum of squared differences of the pixels the
-//                  workgroup owns
+// There is ONE forward tile and ONE backward tile; the other two users are the same tiles with options switched on, under kernel names
+// of their own:
+//   metric_tile    the PSNR / SSIM evaluation metric (utils.py:171-204: quantize + calc_psnr + ssim(val_range=255)): fwd_tile with
+//                  both unit-range images quantised to 0 .. 255 as they are loaded into LDS, L = 255 fixed (no range pass, no range
+//                  word), and next to the SSIM partial sum the integer sum of squared differences of the pixels the workgroup owns
 //   metric_finish  per row: SSIM partial sums in ssim_finish's order -> mean; integer partials as 64 bits -> S, mse = S / (65025 n)
-// Multi-scale SSIM (pytorch_msssim/__init__.py:78-104) is both tiles once more, per level: msssim_level (forward tile + 2 x 2 pooling of the
-// next level's pair + partial extrema of its prediction), msssim_finish (means, product, factors), msssim_bwd_level (coarse to fine); see
-// the section further down.
-// Every window sum is accumulated tap 0 .. 10 in the same association for every pixel, whatever its place in a tile.
+//   msssim_level, msssim_finish, msssim_bwd_level   multi-scale SSIM (pytorch_msssim/__init__.py:78-104), per level: fwd_tile with the
+//                  cs partial sum, the 2 x 2 pooling of the next level's pair and the partial extrema of its prediction; the means,
+//                  product and factors; bwd_tile on the cs or the SSIM map, coarse to fine.  See the section further down.
+// One window table (GN: the windows of 1 .. 11 taps, zero beyond the last tap) and one row-tap function serve every kernel; the
+// single-scale entry points run with taps = 11.  Every window sum is accumulated tap 0 .. 10 in the same association for every pixel,
+// whatever its place in a tile and whichever kernel runs the tile: tests/test_ssim_family_bits_gpu.py holds the users to each other's bits.
 // LDS: lanes run along image columns in every pass, so each ds_read_b32 / ds_write_b32 of a wave touches consecutive
 // words (conflict-free for any row stride); 49 KB (forward) and 59 KB (backward) of static LDS: three resp. two workgroups per CU.
 #include "common.h"
@@ -52,11 +55,33 @@ constexpr int QW = 56;                 // 2 + 52 + 2 patch columns
 constexpr int RANGE_PER_BLOCK = 8192;
 constexpr int RANGE_MAX_BLOCKS = NT;   // partial extrema per row: one per thread of a forward workgroup
 
-// The window of pytorch_msssim.create_window: taps exp(-(i - 5)^2 / 4.5) evaluated in double, rounded to fp32, divided by
-// their fp32 sum.  (The reference multiplies the outer product out in fp32; the separable passes here round differently by
-// < 1 ulp per weight.)
-__device__ __constant__ float G[WIN] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f,
-                                        0x1.b43c3ep-3f,  0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f};
+// The windows of pytorch_msssim.create_window, gaussian(n, 1.5) for n = 1 .. 11 taps: exp(-(i - n / 2)^2 / 4.5) evaluated in double,
+// rounded to fp32, divided by their fp32 sum.  (The reference multiplies the outer product out in fp32; the separable passes here
+// round differently by < 1 ulp per weight.)  Row n - 1 is the window of n taps, zero beyond tap n - 1: every pass runs 11 taps in one
+// association, the trailing products are 0 * (a pixel or the zero fill), and the valid positions are H - n + 1, W - n + 1.  The SSIM
+// loss and the metric use the last row; multi-scale SSIM min(11, H_s, W_s) taps on level s.
+__device__ __constant__ float GN[WIN][WIN] = {
+    {0x1p+0f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.c75814p-2f, 0x1.1c53f6p-1f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.3b3046p-2f, 0x1.899f76p-2f, 0x1.3b3046p-2f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.177ae4p-3f, 0x1.102d28p-2f, 0x1.53e83ep-2f, 0x1.102d28p-2f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.ebd74ep-4f, 0x1.defcdep-3f, 0x1.2b1778p-2f, 0x1.defcdep-3f, 0x1.ebd74ep-4f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.3781f8p-5f, 0x1.d9236ep-4f, 0x1.ccc61cp-3f, 0x1.1fb7eep-2f, 0x1.ccc61cp-3f, 0x1.d9236ep-4f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.2c18a6p-5f, 0x1.c7ce56p-4f, 0x1.bbe4fap-3f, 0x1.152db4p-2f, 0x1.bbe4fap-3f, 0x1.c7ce56p-4f, 0x1.2c18a6p-5f, 0.f, 0.f, 0.f, 0.f},
+    {0x1.f6d8f2p-8f, 0x1.29cb2ep-5f, 0x1.c44f04p-4f, 0x1.b87d0cp-3f, 0x1.130d42p-2f, 0x1.b87d0cp-3f, 0x1.c44f04p-4f, 0x1.29cb2ep-5f, 0.f, 0.f,
+     0.f},
+    {0x1.f304c2p-8f, 0x1.2786b2p-5f, 0x1.c0dd56p-4f, 0x1.b5226ap-3f, 0x1.10f51ap-2f, 0x1.b5226ap-3f, 0x1.c0dd56p-4f, 0x1.2786b2p-5f,
+     0x1.f304c2p-8f, 0.f, 0.f},
+    {0x1.0ddc78p-10f, 0x1.f2813ep-8f, 0x1.2738dp-5f, 0x1.c0670ap-4f, 0x1.b4af36p-3f, 0x1.10ad2ap-2f, 0x1.b4af36p-3f, 0x1.c0670ap-4f,
+     0x1.2738dp-5f, 0x1.f2813ep-8f, 0.f},
+    {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f, 0x1.b43c3ep-3f, 0x1.bff0fep-4f,
+     0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f}};
+
+// the window of `taps` taps, into registers
+__device__ __forceinline__ void load_window(int taps, float (&g)[WIN]) {
+#pragma unroll
+  for (int k = 0; k < WIN; ++k) g[k] = GN[taps - 1][k];
+}
 
 // range word: bit 0 = min(sr) < -0.5, bit 1 = max(sr) > 128  ->  L = (255 or 1) - (-1 or 0); C1 = (0.01 L)^2, C2 = (0.03 L)^2
 // evaluated in double like the reference's Python scalars
@@ -68,12 +93,6 @@ __device__ __forceinline__ void ssim_constants(unsigned cls, float& C1, float& C
   cls &= 3u;
   C1 = cls == 0 ? c1[0] : cls == 1 ? c1[1] : cls == 2 ? c1[2] : c1[3];
   C2 = cls == 0 ? c2[0] : cls == 1 ? c2[1] : cls == 2 ? c2[2] : c2[3];
-}
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, SAVFI_WAVE));
-  return x;
 }
 
 // block-wide max of `hi` and min of `lo`; every thread gets both
@@ -154,17 +173,17 @@ __device__ __forceinline__ void load_patch(const float* __restrict__ plane, floa
   }
 }
 
-// The five window sums of one position of the 11-tap row pass: x, y, x^2, y^2, xy.
-__device__ __forceinline__ void row_taps(const float* __restrict__ x, const float* __restrict__ y, float (&s)[5]) {
+// The five window sums of one position of the 11-tap row pass under window g: x, y, x^2, y^2, xy.
+__device__ __forceinline__ void row_taps_n(const float (&g)[WIN], const float* __restrict__ x, const float* __restrict__ y, float (&s)[5]) {
   s[0] = s[1] = s[2] = s[3] = s[4] = 0.f;
 #pragma unroll
   for (int k = 0; k < WIN; ++k) {
-    const float g = G[k], a = x[k], b = y[k];
-    s[0] = fmaf(g, a, s[0]);
-    s[1] = fmaf(g, b, s[1]);
-    s[2] = fmaf(g, a * a, s[2]);
-    s[3] = fmaf(g, b * b, s[3]);
-    s[4] = fmaf(g, a * b, s[4]);
+    const float a = x[k], b = y[k];
+    s[0] = fmaf(g[k], a, s[0]);
+    s[1] = fmaf(g[k], b, s[1]);
+    s[2] = fmaf(g[k], a * a, s[2]);
+    s[3] = fmaf(g[k], b * b, s[3]);
+    s[4] = fmaf(g[k], a * b, s[4]);
   }
 }
 
@@ -187,45 +206,56 @@ __device__ __forceinline__ float ssim_value(const float (&m)[5], float C1, float
 // NaN word of a workgroup's squared-error partial (a workgroup's sum stays below 2^27, see metric_tile)
 constexpr unsigned SQ_NAN = 0xffffffffu;
 
-// One forward tile, for both kernels below.  grid (tiles_x, tiles_y, rows * C); partial[(z * tiles_y + by) * tiles_x + bx].
-// METRIC: the patches are quantised on load, the range class is 2 (L = 255: no extrema, no range word), and the workgroup also adds
-// (q_p - q_t)^2 as an integer over the pixels it owns -> sq_partial (same index).  Every pixel of the plane has one owner: the
-// tiles step over the SSIM positions, so the last tile row / column also own the 10 trailing pixel rows / columns, which lie
-// inside their patch (<= 26 x 74 pixels * 65025 < 2^27: the 32-bit sum is exact).  A NaN among the owned pixels -> SQ_NAN.
-// msssim_level below is a second copy of this tile (and row_taps_n of row_taps): a fix here has to be made there too.
-template <bool METRIC>
+// THE forward tile, of every kernel below that computes an SSIM map.  grid (tiles_x, tiles_y, rows * C) over the (H - taps + 1) x
+// (W - taps + 1) positions; the workgroup's index w = (z * tiles_y + by) * tiles_x + bx; partial[w] = its SSIM sum.
+// The range class: fixed_cls, or (fixed_cls < 0) from `ext`, the ext_blocks (max, min) pairs of this row's prediction; the first
+// workgroup of a row publishes it in *cls_word (the word of ITS row; NULL: nobody asks).
+// Every pixel of the plane has one owner: the tiles step over the SSIM positions, so the last tile row / column also own the trailing
+// pixel rows / columns, which lie inside their patch.  The options work on the owned pixels, out of the LDS patches:
+//   QUANT  the patches are quantised on load
+//   SQERR  the workgroup also adds (x - y)^2 of the (quantised) pair as an integer -> sq_partial[w] (<= 26 x 74 pixels * 65025 < 2^27:
+//          the 32-bit sum is exact); a NaN among the owned pixels -> SQ_NAN
+//   MULTI  the cs map v1 / v2 is summed too -> partial[total + w], and unless pool1 is NULL (the last level) the pair is pooled for the
+//          next level: pool1 / pool2 [rows * C, H / 2, W / 2] averages, ((a + b) + c) + d over (0,0) (0,1) (1,0) (1,1), times 0.25 --
+//          avg_pool2d's order; ext_out[2 w] = max, min of the pooled prediction values this workgroup wrote (the next level's `ext`: the
+//          pooled pair is not read again for it).  TH and TW are even, so no 2 x 2 block straddles two owners.
+template <bool QUANT, bool SQERR, bool MULTI>
 __device__ __forceinline__ void fwd_tile(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
-                                         int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word, float* __restrict__ partial,
-                                         unsigned* __restrict__ sq_partial, int C, int H, int W, int vec_ok) {
+                                         int ext_blocks, int fixed_cls, unsigned* __restrict__ cls_word, float* __restrict__ partial,
+                                         unsigned* __restrict__ sq_partial, float* __restrict__ pool1, float* __restrict__ pool2,
+                                         float* __restrict__ ext_out, int row, int H, int W, int taps, int vec_ok) {
   __shared__ __attribute__((aligned(16))) float px[PH * PW];
   __shared__ __attribute__((aligned(16))) float py[PH * PW];
   __shared__ float rf[5][PH][TW];
   __shared__ float red[2 * NW];
-  const int z = blockIdx.z, row = z / C;
+  const int z = blockIdx.z;
   const int y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
-  const int Ho = H - HALO, Wo = W - HALO;
+  const int Ho = H - taps + 1, Wo = W - taps + 1;
   const size_t plane = (size_t)z * H * W;
-  load_patch<PH, PW, METRIC>(sr + plane, px, y0, x0, H, W, vec_ok);
-  load_patch<PH, PW, METRIC>(hr + plane, py, y0, x0, H, W, vec_ok);
-  // the row's range class: from its partial extrema (<= NT of them), or the fixed one
+  const size_t wg = ((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  const int own_h = blockIdx.y + 1 == gridDim.y ? H - y0 : TH, own_w = blockIdx.x + 1 == gridDim.x ? W - x0 : TW;
+  load_patch<PH, PW, QUANT>(sr + plane, px, y0, x0, H, W, vec_ok);
+  load_patch<PH, PW, QUANT>(hr + plane, py, y0, x0, H, W, vec_ok);
   unsigned cls = (unsigned)fixed_cls;
-  if (!METRIC && fixed_cls < 0) {
+  if (fixed_cls < 0) {
     float hi = -INFINITY, lo = INFINITY;
-    if ((int)threadIdx.x < ext_blocks) {
-      hi = ext[((size_t)row * ext_blocks + threadIdx.x) * 2];
-      lo = ext[((size_t)row * ext_blocks + threadIdx.x) * 2 + 1];
+    const float* e = ext + (size_t)row * ext_blocks * 2;
+    for (int i = threadIdx.x; i < ext_blocks; i += NT) {
+      hi = fmaxf(hi, e[2 * i]);
+      lo = fminf(lo, e[2 * i + 1]);
     }
     block_extrema(hi, lo, red);
     cls = (lo < -0.5f ? 1u : 0u) | (hi > 128.f ? 2u : 0u);
   }
-  if (!METRIC && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && z == row * C) range_word[row] = cls;
+  if (cls_word && threadIdx.x == 0) *cls_word = cls;
   float C1, C2;
   ssim_constants(cls, C1, C2);
+  float g[WIN];
+  load_window(taps, g);
   __syncthreads();
 
-  if constexpr (METRIC) {
+  if constexpr (SQERR) {
     __shared__ unsigned sq_red[NW];
-    const int own_h = blockIdx.y + 1 == gridDim.y ? H - y0 : TH, own_w = blockIdx.x + 1 == gridDim.x ? W - x0 : TW;
     unsigned acc = 0;
     int bad = 0;
     for (int i = threadIdx.x; i < own_h * own_w; i += NT) {
@@ -245,287 +275,11 @@ __device__ __forceinline__ void fwd_tile(const float* __restrict__ sr, const flo
       unsigned tot = 0;
 #pragma unroll
       for (int w = 0; w < NW; ++w) tot += sq_red[w];
-      sq_partial[((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = bad ? SQ_NAN : tot;
+      sq_partial[wg] = bad ? SQ_NAN : tot;
     }
   }
 
-  for (int i = threadIdx.x; i < PH * TW; i += NT) {
-    const int r = i / TW, c = i - r * TW;
-    float s[5];
-    row_taps(px + r * PW + c, py + r * PW + c, s);
-#pragma unroll
-    for (int p = 0; p < 5; ++p) rf[p][r][c] = s[p];
-  }
-  __syncthreads();
-
-  // column pass: thread = one column, four consecutive rows (14 values of every plane slide through registers)
-  const int c = threadIdx.x & (TW - 1), r0 = (threadIdx.x / TW) * 4;
-  float mom[4][5];
-#pragma unroll
-  for (int p = 0; p < 5; ++p) {
-    float v[4 + HALO];
-#pragma unroll
-    for (int k = 0; k < 4 + HALO; ++k) v[k] = rf[p][r0 + k][c];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; ++k) acc = fmaf(G[k], v[o + k], acc);
-      mom[o][p] = acc;
-    }
-  }
-  float sum = 0.f;
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    float r1, r2, B1, B2;
-    const float v = ssim_value(mom[o], C1, C2, r1, r2, B1, B2);
-    if (y0 + r0 + o < Ho && x0 + c < Wo) sum += v;
-  }
-  const float tot = block_sum<NW>(sum, red);
-  if (threadIdx.x == 0) partial[((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
-                                               int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word,
-                                               float* __restrict__ partial, int C, int H, int W, int vec_ok) {
-  fwd_tile<false>(sr, hr, ext, ext_blocks, fixed_cls, range_word, partial, nullptr, C, H, W, vec_ok);
-}
-
-// the metric's tile kernel: unit-range pred / target in, SSIM partial sum and integer squared-error partial out
-__global__ __launch_bounds__(NT) void metric_tile(const float* __restrict__ pred, const float* __restrict__ target,
-                                                  float* __restrict__ partial, unsigned* __restrict__ sq_partial, int C, int H, int W,
-                                                  int vec_ok) {
-  fwd_tile<true>(pred, target, nullptr, 0, 2, nullptr, partial, sq_partial, C, H, W, vec_ok);
-}
-
-// result[row] = (1 - (the row's partial sums, lane-strided then a butterfly: always the same order) / n) / 2
-__global__ __launch_bounds__(64) void ssim_finish(const float* __restrict__ partial, float* __restrict__ result, int blocks, float n) {
-  const float* p = partial + (size_t)blockIdx.x * blocks;
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 64) acc += p[i];
-  acc = wave_sum(acc);
-  if (threadIdx.x == 0) result[blockIdx.x] = (1.f - acc / n) / 2.f;
-}
-
-// result[row] = {mse, ssim}: the SSIM partial sums in ssim_finish's order / n_out; the squared-error partials as 64-bit integers
-// (exact, whatever the order) -> S / (65025 n_pix) in double.  A NaN word makes the mse NaN (the SSIM sum then is NaN by itself:
-// every pixel lies in some window) and sq_sum[row] all ones.
-__global__ __launch_bounds__(64) void metric_finish(const float* __restrict__ partial, const unsigned* __restrict__ sq_partial,
-                                                    float* __restrict__ result, unsigned long long* __restrict__ sq_sum, int blocks,
-                                                    float n_out, double n_pix) {
-  const float* p = partial + (size_t)blockIdx.x * blocks;
-  const unsigned* q = sq_partial + (size_t)blockIdx.x * blocks;
-  float acc = 0.f;
-  unsigned long long S = 0;
-  int bad = 0;
-  for (int i = threadIdx.x; i < blocks; i += 64) {
-    acc += p[i];
-    const unsigned w = q[i];
-    bad |= w == SQ_NAN;
-    S += w;
-  }
-  acc = wave_sum(acc);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)S, off, SAVFI_WAVE), hi = (unsigned)__shfl_xor((int)(unsigned)(S >> 32), off, SAVFI_WAVE);
-    S += ((unsigned long long)hi << 32) | lo;
-    bad |= __shfl_xor(bad, off, SAVFI_WAVE);
-  }
-  if (threadIdx.x == 0) {
-    result[2 * blockIdx.x] = bad ? __builtin_nanf("") : (float)((double)S / (65025.0 * n_pix));
-    result[2 * blockIdx.x + 1] = acc / n_out;
-    if (sq_sum) sq_sum[blockIdx.x] = bad ? ~0ULL : S;
-  }
-}
-
-// grid (cdiv(W, BW), cdiv(H, BH), rows * C).  msssim_bwd_level below is a second copy of this kernel: a fix here has to be made there too.
-__global__ __launch_bounds__(NT) void ssim_bwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ g_loss,
-                                               const unsigned* __restrict__ range_word, float* __restrict__ g_sr, int C, int H, int W,
-                                               float inv_2n, int vec_ok) {
-  __shared__ __attribute__((aligned(16))) float px[QH * QW];
-  __shared__ __attribute__((aligned(16))) float py[QH * QW];
-  __shared__ float rf[5][QH][CW];                  // row-filtered moments; later the row-filtered coefficients [3][CH][BW]
-  __shared__ float coef[3][CH][CW];
-  float(*ar)[CH][BW] = reinterpret_cast<float(*)[CH][BW]>(&rf[0][0][0]);
-  static_assert(3 * CH * BW <= 5 * QH * CW, "the row-filtered coefficients reuse the moments' planes");
-  const int z = blockIdx.z, row = z / C;
-  const int y0 = blockIdx.y * BH, x0 = blockIdx.x * BW;
-  const int Ho = H - HALO, Wo = W - HALO;
-  const size_t plane = (size_t)z * H * W;
-  load_patch<QH, QW>(sr + plane, px, y0 - HALO, x0 - QX, H, W, vec_ok);
-  load_patch<QH, QW>(hr + plane, py, y0 - HALO, x0 - QX, H, W, vec_ok);
-  float C1, C2;
-  ssim_constants(range_word[row], C1, C2);
-  __syncthreads();
-
-  // moments, row pass: SSIM column cc is position x0 - 10 + cc, its window starts at patch column cc + 2
-  for (int i = threadIdx.x; i < QH * CW; i += NT) {
-    const int r = i / CW, cc = i - r * CW;
-    float s[5];
-    row_taps(px + r * QW + cc + (QX - HALO), py + r * QW + cc + (QX - HALO), s);
-#pragma unroll
-    for (int p = 0; p < 5; ++p) rf[p][r][cc] = s[p];
-  }
-  __syncthreads();
-
-  // moments, column pass, and the coefficient planes (zero outside the valid SSIM positions)
-  for (int i = threadIdx.x; i < CH * CW; i += NT) {
-    const int cr = i / CW, cc = i - cr * CW;
-    const int oy = y0 - HALO + cr, ox = x0 - HALO + cc;
-    float a = 0.f, b = 0.f, c = 0.f;
-    if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
-      float m[5];
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) acc = fmaf(G[k], rf[p][cr + k][cc], acc);
-        m[p] = acc;
-      }
-      float r1, r2, B1, B2;
-      const float v = ssim_value(m, C1, C2, r1, r2, B1, B2);
-      {
-#pragma clang fp contract(off)
-        // an identical pair gives v = r1 = r2 = 1: then c == -2 b, dm == 0 and a == 0 exactly, and so is the gradient
-        b = -v / B2;
-        c = (2.f * r1) / B2;
-        const float dm = ((2.f * m[1]) * r2) / B1 - ((2.f * m[0]) * v) / B1;
-        a = (dm - (2.f * m[0]) * b) - m[1] * c;
-      }
-    }
-    coef[0][cr][cc] = a;
-    coef[1][cr][cc] = b;
-    coef[2][cr][cc] = c;
-  }
-  __syncthreads();      // every read of rf is done: `ar` reuses it
-
-  // adjoint, row pass: pixel column ix gathers G[k] * coef[position ix - k] = coef column ix + 10 - k
-  for (int i = threadIdx.x; i < CH * BW; i += NT) {
-    const int cr = i / BW, ix = i - cr * BW;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; ++k) acc = fmaf(G[k], coef[p][cr][ix + HALO - k], acc);
-      ar[p][cr][ix] = acc;
-    }
-  }
-  __syncthreads();
-
-  // adjoint, column pass, and the gradient
-  const float scale = -g_loss[row] * inv_2n;
-  for (int i = threadIdx.x; i < BH * BW; i += NT) {
-    const int iy = i / BW, ix = i - iy * BW;
-    const int gy = y0 + iy, gx = x0 + ix;
-    float t[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; ++k) acc = fmaf(G[k], ar[p][iy + HALO - k][ix], acc);
-      t[p] = acc;
-    }
-    if (gy < H && gx < W) {
-#pragma clang fp contract(off)
-      const float x = px[(iy + HALO) * QW + ix + QX], y = py[(iy + HALO) * QW + ix + QX];
-      g_sr[plane + (size_t)gy * W + gx] = scale * ((t[0] + (2.f * x) * t[1]) + y * t[2]);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// Multi-scale SSIM (pytorch_msssim/__init__.py:78-104, "as implemented"): five levels, each the SSIM map and the cs map v1 / v2 of
-// one image pair under the window of min(11, H_s, W_s) taps, then both images 2 x 2 averaged (floor).  Result
-// ssim_4 ^ (4 w_4) * prod_{s < 4} cs_s ^ w_s (the reference's prod(pow1[:-1] * pow2[-1])).
-//   msssim_level   the forward tile once more: SSIM and cs partial sums of one level, and out of the same LDS patches the 2 x 2
-//                  averages of the pixels the workgroup owns (both images, the next level's operands) and the partial extrema of
-//                  the pooled prediction (the next level's range class: the pooled pair is not read again for it)
-//   msssim_finish  per row: the ten means (partial sums in a fixed order), the result, and the ten factors d out / d mean
-//   msssim_bwd_level  coarse to fine, ssim_bwd once more: the level's own map gradient (cs map on levels 0 .. 3, SSIM map on level 4:
-//                  the other factors are identically zero) plus a quarter of the next-coarser level's gradient, replicated
-// A window of n < 11 taps is the table row below, zero beyond tap n - 1: every pass still runs 11 taps in ssim_fwd's association
-// (the n = 11 row is G), the trailing products are 0 * (a pixel or the zero fill), and the valid positions are H - n + 1, W - n + 1.
-// ------------------------------------------------------------------------------------------------------------------------
-constexpr int MS_LEVELS = 5;
-constexpr int MS_HEAD = 16;      // 32-bit words per row at the start of the scratch: 10 factors, 5 class words, 1 spare
-
-// gaussian(n, 1.5) of pytorch_msssim for n = 1 .. 11: exp(-(i - n / 2)^2 / 4.5) in double, rounded to fp32, divided by the fp32 sum
-__device__ __constant__ float GN[WIN][WIN] = {
-    {0x1p+0f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.c75814p-2f, 0x1.1c53f6p-1f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.3b3046p-2f, 0x1.899f76p-2f, 0x1.3b3046p-2f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.177ae4p-3f, 0x1.102d28p-2f, 0x1.53e83ep-2f, 0x1.102d28p-2f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.ebd74ep-4f, 0x1.defcdep-3f, 0x1.2b1778p-2f, 0x1.defcdep-3f, 0x1.ebd74ep-4f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.3781f8p-5f, 0x1.d9236ep-4f, 0x1.ccc61cp-3f, 0x1.1fb7eep-2f, 0x1.ccc61cp-3f, 0x1.d9236ep-4f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.2c18a6p-5f, 0x1.c7ce56p-4f, 0x1.bbe4fap-3f, 0x1.152db4p-2f, 0x1.bbe4fap-3f, 0x1.c7ce56p-4f, 0x1.2c18a6p-5f, 0.f, 0.f, 0.f, 0.f},
-    {0x1.f6d8f2p-8f, 0x1.29cb2ep-5f, 0x1.c44f04p-4f, 0x1.b87d0cp-3f, 0x1.130d42p-2f, 0x1.b87d0cp-3f, 0x1.c44f04p-4f, 0x1.29cb2ep-5f, 0.f, 0.f,
-     0.f},
-    {0x1.f304c2p-8f, 0x1.2786b2p-5f, 0x1.c0dd56p-4f, 0x1.b5226ap-3f, 0x1.10f51ap-2f, 0x1.b5226ap-3f, 0x1.c0dd56p-4f, 0x1.2786b2p-5f,
-     0x1.f304c2p-8f, 0.f, 0.f},
-    {0x1.0ddc78p-10f, 0x1.f2813ep-8f, 0x1.2738dp-5f, 0x1.c0670ap-4f, 0x1.b4af36p-3f, 0x1.10ad2ap-2f, 0x1.b4af36p-3f, 0x1.c0670ap-4f,
-     0x1.2738dp-5f, 0x1.f2813ep-8f, 0.f},
-    {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f, 0x1.b43c3ep-3f, 0x1.bff0fep-4f,
-     0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f}};
-
-__device__ __forceinline__ void row_taps_n(const float (&g)[WIN], const float* __restrict__ x, const float* __restrict__ y, float (&s)[5]) {
-  s[0] = s[1] = s[2] = s[3] = s[4] = 0.f;
-#pragma unroll
-  for (int k = 0; k < WIN; ++k) {
-    const float a = x[k], b = y[k];
-    s[0] = fmaf(g[k], a, s[0]);
-    s[1] = fmaf(g[k], b, s[1]);
-    s[2] = fmaf(g[k], a * a, s[2]);
-    s[3] = fmaf(g[k], b * b, s[3]);
-    s[4] = fmaf(g[k], a * b, s[4]);
-  }
-}
-
-// One level's forward tile.  grid (tiles_x, tiles_y, rows * C) over the (H - n + 1) x (W - n + 1) positions; the workgroup's index
-// w = (z * tiles_y + by) * tiles_x + bx.  partial[w] = SSIM sum, partial[total + w] = cs sum.  ext: the partial extrema of this
-// level's prediction, ext_blocks (max, min) pairs per row (ssim_range's on level 0, the previous level's workgroups' after that).
-// pool1 / pool2 (NULL on the last level): [rows * C, H / 2, W / 2] averages, ((a + b) + c) + d over (0,0) (0,1) (1,0) (1,1), times
-// 0.25 -- avg_pool2d's order; ext_out[2 w] = max, min of the pooled prediction values this workgroup wrote.  Pixel ownership is
-// metric_tile's: TH and TW are even, so no 2 x 2 block straddles two owners.
-// SECOND COPY: the staging, the row and column passes and the map arithmetic restate fwd_tile (and row_taps_n restates row_taps)
-// rather than sharing code with it, so that the single-scale kernels keep their bits.  A fix to the tile has to be made in both places.
-template <bool QUANT>
-__global__ __launch_bounds__(NT) void msssim_level(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
-                                                   int ext_blocks, int fixed_cls, unsigned* __restrict__ head, int level,
-                                                   float* __restrict__ partial, float* __restrict__ pool1, float* __restrict__ pool2,
-                                                   float* __restrict__ ext_out, int C, int H, int W, int taps, int vec_ok) {
-  __shared__ __attribute__((aligned(16))) float px[PH * PW];
-  __shared__ __attribute__((aligned(16))) float py[PH * PW];
-  __shared__ float rf[5][PH][TW];
-  __shared__ float red[2 * NW];
-  const int z = blockIdx.z, row = z / C;
-  const int y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
-  const int Ho = H - taps + 1, Wo = W - taps + 1;
-  const size_t plane = (size_t)z * H * W;
-  const size_t wg = ((size_t)z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  const size_t wgs = (size_t)gridDim.z * gridDim.y * gridDim.x;
-  load_patch<PH, PW, QUANT>(sr + plane, px, y0, x0, H, W, vec_ok);
-  load_patch<PH, PW, QUANT>(hr + plane, py, y0, x0, H, W, vec_ok);
-  unsigned cls = (unsigned)fixed_cls;
-  if (fixed_cls < 0) {
-    float hi = -INFINITY, lo = INFINITY;
-    const float* e = ext + (size_t)row * ext_blocks * 2;
-    for (int i = threadIdx.x; i < ext_blocks; i += NT) {
-      hi = fmaxf(hi, e[2 * i]);
-      lo = fminf(lo, e[2 * i + 1]);
-    }
-    block_extrema(hi, lo, red);
-    cls = (lo < -0.5f ? 1u : 0u) | (hi > 128.f ? 2u : 0u);
-  }
-  if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && z == row * C) head[(size_t)row * MS_HEAD + 2 * MS_LEVELS + level] = cls;
-  float C1, C2;
-  ssim_constants(cls, C1, C2);
-  float g[WIN];
-#pragma unroll
-  for (int k = 0; k < WIN; ++k) g[k] = GN[taps - 1][k];
-  __syncthreads();
-
-  if (pool1) {
-    const int own_h = blockIdx.y + 1 == gridDim.y ? H - y0 : TH, own_w = blockIdx.x + 1 == gridDim.x ? W - x0 : TW;
+  if (MULTI && pool1) {
     const int ph = own_h / 2, pw = own_w / 2, H2 = H / 2, W2 = W / 2;
     const size_t pplane = (size_t)z * H2 * W2;
     float hi = -INFINITY, lo = INFINITY;
@@ -557,6 +311,7 @@ __global__ __launch_bounds__(NT) void msssim_level(const float* __restrict__ sr,
   }
   __syncthreads();
 
+  // column pass: thread = one column, four consecutive rows (14 values of every plane slide through registers)
   const int c = threadIdx.x & (TW - 1), r0 = (threadIdx.x / TW) * 4;
   float mom[4][5];
 #pragma unroll
@@ -579,15 +334,225 @@ __global__ __launch_bounds__(NT) void msssim_level(const float* __restrict__ sr,
     const float v = ssim_value(mom[o], C1, C2, r1, r2, B1, B2);
     if (y0 + r0 + o < Ho && x0 + c < Wo) {
       sum += v;
-      cs += r2;
+      if constexpr (MULTI) cs += r2;
     }
   }
   const float tot = block_sum<NW>(sum, red);
-  const float tcs = block_sum<NW>(cs, red);
-  if (threadIdx.x == 0) {
-    partial[wg] = tot;
-    partial[wgs + wg] = tcs;
+  if (threadIdx.x == 0) partial[wg] = tot;
+  if constexpr (MULTI) {
+    const float tcs = block_sum<NW>(cs, red);
+    if (threadIdx.x == 0) partial[(size_t)gridDim.z * gridDim.y * gridDim.x + wg] = tcs;
   }
+}
+
+// the word of row `row` for its first workgroup, NULL for every other one
+__device__ __forceinline__ unsigned* first_of_row(unsigned* word, int row, int C) {
+  return blockIdx.x == 0 && blockIdx.y == 0 && (int)blockIdx.z == row * C ? word : nullptr;
+}
+
+__global__ __launch_bounds__(NT) void ssim_fwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
+                                               int ext_blocks, int fixed_cls, unsigned* __restrict__ range_word,
+                                               float* __restrict__ partial, int C, int H, int W, int vec_ok) {
+  const int row = blockIdx.z / C;
+  fwd_tile<false, false, false>(sr, hr, ext, ext_blocks, fixed_cls, first_of_row(range_word + row, row, C), partial, nullptr, nullptr,
+                                nullptr, nullptr, row, H, W, WIN, vec_ok);
+}
+
+// the metric's tile kernel: unit-range pred / target in, SSIM partial sum and integer squared-error partial out; L = 255
+__global__ __launch_bounds__(NT) void metric_tile(const float* __restrict__ pred, const float* __restrict__ target,
+                                                  float* __restrict__ partial, unsigned* __restrict__ sq_partial, int C, int H, int W,
+                                                  int vec_ok) {
+  fwd_tile<true, true, false>(pred, target, nullptr, 0, 2, nullptr, partial, sq_partial, nullptr, nullptr, nullptr, 0, H, W, WIN, vec_ok);
+}
+
+// the sum of `blocks` partial sums by one wave: lane-strided, then a butterfly -- always the same order; every lane gets it.
+// also(i) runs in the same pass for whatever else the caller gathers per workgroup (one walk over the row: the loop is latency-bound).
+template <typename F>
+__device__ __forceinline__ float row_sum(const float* __restrict__ p, int blocks, F also) {
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < blocks; i += 64) {
+    acc += p[i];
+    also(i);
+  }
+  return wave_sum(acc);
+}
+
+// result[row] = (1 - (the row's partial sums) / n) / 2
+__global__ __launch_bounds__(64) void ssim_finish(const float* __restrict__ partial, float* __restrict__ result, int blocks, float n) {
+  const float acc = row_sum(partial + (size_t)blockIdx.x * blocks, blocks, [](int) {});
+  if (threadIdx.x == 0) result[blockIdx.x] = (1.f - acc / n) / 2.f;
+}
+
+// result[row] = {mse, ssim}: the SSIM partial sums in ssim_finish's order / n_out; the squared-error partials as 64-bit integers
+// (exact, whatever the order) -> S / (65025 n_pix) in double.  A NaN word makes the mse NaN (the SSIM sum then is NaN by itself:
+// every pixel lies in some window) and sq_sum[row] all ones.
+__global__ __launch_bounds__(64) void metric_finish(const float* __restrict__ partial, const unsigned* __restrict__ sq_partial,
+                                                    float* __restrict__ result, unsigned long long* __restrict__ sq_sum, int blocks,
+                                                    float n_out, double n_pix) {
+  const unsigned* q = sq_partial + (size_t)blockIdx.x * blocks;
+  unsigned long long S = 0;
+  int bad = 0;
+  const float acc = row_sum(partial + (size_t)blockIdx.x * blocks, blocks, [&](int i) {
+    const unsigned w = q[i];
+    bad |= w == SQ_NAN;
+    S += w;
+  });
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)S, off, SAVFI_WAVE), hi = (unsigned)__shfl_xor((int)(unsigned)(S >> 32), off, SAVFI_WAVE);
+    S += ((unsigned long long)hi << 32) | lo;
+    bad |= __shfl_xor(bad, off, SAVFI_WAVE);
+  }
+  if (threadIdx.x == 0) {
+    result[2 * blockIdx.x] = bad ? __builtin_nanf("") : (float)((double)S / (65025.0 * n_pix));
+    result[2 * blockIdx.x + 1] = acc / n_out;
+    if (sq_sum) sq_sum[blockIdx.x] = bad ? ~0ULL : S;
+  }
+}
+
+// THE backward tile.  grid (cdiv(W, BW), cdiv(H, BH), rows * C): g_sr = scale * (the gradient of the sum of a map under the window of
+// `taps` taps and range class `cls`) + a quarter of g_coarse, replicated.  SSIM_MAP: the SSIM map, else the cs map v1 / v2.
+// g_coarse (NULL: none): the gradient of the next-coarser level [rows * C, H / 2, W / 2]; a pixel whose 2 x 2 block was dropped by the
+// floor gets nothing from it.
+template <bool SSIM_MAP>
+__device__ __forceinline__ void bwd_tile(const float* __restrict__ sr, const float* __restrict__ hr, unsigned cls, float scale,
+                                         const float* __restrict__ g_coarse, float* __restrict__ g_sr, int H, int W, int taps,
+                                         int vec_ok) {
+  __shared__ __attribute__((aligned(16))) float px[QH * QW];
+  __shared__ __attribute__((aligned(16))) float py[QH * QW];
+  __shared__ float rf[5][QH][CW];                  // row-filtered moments; later the row-filtered coefficients [3][CH][BW]
+  __shared__ float coef[3][CH][CW];
+  float(*ar)[CH][BW] = reinterpret_cast<float(*)[CH][BW]>(&rf[0][0][0]);
+  static_assert(3 * CH * BW <= 5 * QH * CW, "the row-filtered coefficients reuse the moments' planes");
+  const int z = blockIdx.z;
+  const int y0 = blockIdx.y * BH, x0 = blockIdx.x * BW;
+  const int Ho = H - taps + 1, Wo = W - taps + 1;
+  const size_t plane = (size_t)z * H * W;
+  load_patch<QH, QW>(sr + plane, px, y0 - HALO, x0 - QX, H, W, vec_ok);
+  load_patch<QH, QW>(hr + plane, py, y0 - HALO, x0 - QX, H, W, vec_ok);
+  float C1, C2;
+  ssim_constants(cls, C1, C2);
+  float g[WIN];
+  load_window(taps, g);
+  __syncthreads();
+
+  // moments, row pass: SSIM column cc is position x0 - 10 + cc, its window starts at patch column cc + 2
+  for (int i = threadIdx.x; i < QH * CW; i += NT) {
+    const int r = i / CW, cc = i - r * CW;
+    float s[5];
+    row_taps_n(g, px + r * QW + cc + (QX - HALO), py + r * QW + cc + (QX - HALO), s);
+#pragma unroll
+    for (int p = 0; p < 5; ++p) rf[p][r][cc] = s[p];
+  }
+  __syncthreads();
+
+  // moments, column pass, and the coefficient planes (zero outside the valid SSIM positions)
+  for (int i = threadIdx.x; i < CH * CW; i += NT) {
+    const int cr = i / CW, cc = i - cr * CW;
+    const int oy = y0 - HALO + cr, ox = x0 - HALO + cc;
+    float a = 0.f, b = 0.f, c = 0.f;
+    if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
+      float m[5];
+#pragma unroll
+      for (int p = 0; p < 5; ++p) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], rf[p][cr + k][cc], acc);
+        m[p] = acc;
+      }
+      float r1, r2, B1, B2;
+      const float v = ssim_value(m, C1, C2, r1, r2, B1, B2);
+      {
+#pragma clang fp contract(off)
+        if constexpr (SSIM_MAP) {
+          // an identical pair gives v = r1 = r2 = 1: then c == -2 b, dm == 0 and a == 0 exactly, and so is the gradient
+          b = -v / B2;
+          c = (2.f * r1) / B2;
+          const float dm = ((2.f * m[1]) * r2) / B1 - ((2.f * m[0]) * v) / B1;
+          a = (dm - (2.f * m[0]) * b) - m[1] * c;
+        } else {
+          // cs = A2 / B2 does not see mu1 but through s1 and s12; an identical pair gives r2 = 1, c == -2 b and a == 0 exactly
+          b = -r2 / B2;
+          c = 2.f / B2;
+          a = (0.f - (2.f * m[0]) * b) - m[1] * c;
+        }
+      }
+    }
+    coef[0][cr][cc] = a;
+    coef[1][cr][cc] = b;
+    coef[2][cr][cc] = c;
+  }
+  __syncthreads();      // every read of rf is done: `ar` reuses it
+
+  // adjoint, row pass: pixel column ix gathers G[k] * coef[position ix - k] = coef column ix + 10 - k
+  for (int i = threadIdx.x; i < CH * BW; i += NT) {
+    const int cr = i / BW, ix = i - cr * BW;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], coef[p][cr][ix + HALO - k], acc);
+      ar[p][cr][ix] = acc;
+    }
+  }
+  __syncthreads();
+
+  // adjoint, column pass, and the gradient
+  const int H2 = H / 2, W2 = W / 2;
+  for (int i = threadIdx.x; i < BH * BW; i += NT) {
+    const int iy = i / BW, ix = i - iy * BW;
+    const int gy = y0 + iy, gx = x0 + ix;
+    float t[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], ar[p][iy + HALO - k][ix], acc);
+      t[p] = acc;
+    }
+    if (gy < H && gx < W) {
+#pragma clang fp contract(off)
+      const float x = px[(iy + HALO) * QW + ix + QX], y = py[(iy + HALO) * QW + ix + QX];
+      float v = scale * ((t[0] + (2.f * x) * t[1]) + y * t[2]);
+      if (g_coarse && (gy >> 1) < H2 && (gx >> 1) < W2) v += 0.25f * g_coarse[(size_t)z * H2 * W2 + (size_t)(gy >> 1) * W2 + (gx >> 1)];
+      g_sr[plane + (size_t)gy * W + gx] = v;
+    }
+  }
+}
+
+// d loss / d sr of the SSIM loss: the SSIM map's gradient times -g / (2 n)
+__global__ __launch_bounds__(NT) void ssim_bwd(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ g_loss,
+                                               const unsigned* __restrict__ range_word, float* __restrict__ g_sr, int C, int H, int W,
+                                               float inv_2n, int vec_ok) {
+  const int row = blockIdx.z / C;
+  bwd_tile<true>(sr, hr, range_word[row], -g_loss[row] * inv_2n, nullptr, g_sr, H, W, WIN, vec_ok);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Multi-scale SSIM (pytorch_msssim/__init__.py:78-104, "as implemented"): five levels, each the SSIM map and the cs map v1 / v2 of
+// one image pair under the window of min(11, H_s, W_s) taps, then both images 2 x 2 averaged (floor).  Result
+// ssim_4 ^ (4 w_4) * prod_{s < 4} cs_s ^ w_s (the reference's prod(pow1[:-1] * pow2[-1])).
+//   msssim_level   fwd_tile with MULTI: SSIM and cs partial sums of one level, and out of the same LDS patches the 2 x 2 averages of
+//                  the pixels the workgroup owns (both images, the next level's operands) and the partial extrema of the pooled
+//                  prediction (the next level's range class)
+//   msssim_finish  per row: the ten means (partial sums in a fixed order), the result, and the ten factors d out / d mean
+//   msssim_bwd_level  coarse to fine, bwd_tile: the level's own map gradient (cs map on levels 0 .. 3, SSIM map on level 4: the
+//                  other factors are identically zero) plus a quarter of the next-coarser level's gradient, replicated
+// The kernels here add nothing to the tiles but where a level's class word, factor and window length are found.
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int MS_LEVELS = 5;
+constexpr int MS_HEAD = 16;      // 32-bit words per row at the start of the scratch: 10 factors, 5 class words, 1 spare
+
+// One level of the forward.  ext: ssim_range's partial extrema on level 0, the previous level's workgroups' after that; QUANT only on
+// level 0 (the metric: the pooled pair then is the quantised one's).
+template <bool QUANT>
+__global__ __launch_bounds__(NT) void msssim_level(const float* __restrict__ sr, const float* __restrict__ hr, const float* __restrict__ ext,
+                                                   int ext_blocks, int fixed_cls, unsigned* __restrict__ head, int level,
+                                                   float* __restrict__ partial, float* __restrict__ pool1, float* __restrict__ pool2,
+                                                   float* __restrict__ ext_out, int C, int H, int W, int taps, int vec_ok) {
+  const int row = blockIdx.z / C;
+  fwd_tile<QUANT, false, true>(sr, hr, ext, ext_blocks, fixed_cls, first_of_row(head + (size_t)row * MS_HEAD + 2 * MS_LEVELS + level, row, C),
+                               partial, nullptr, pool1, pool2, ext_out, row, H, W, taps, vec_ok);
 }
 
 struct MsFinish {
@@ -608,12 +573,8 @@ __global__ __launch_bounds__(64) void msssim_finish(const float* __restrict__ sc
 #pragma unroll
   for (int s = 0; s < MS_LEVELS; ++s) {
     const float* p = scratch + f.partial[s] + (size_t)row * f.blocks[s];
-    float a = 0.f, b = 0.f;
-    for (int i = threadIdx.x; i < f.blocks[s]; i += 64) {
-      a += p[i];
-      b += p[f.wgs[s] + i];
-    }
-    ms[s] = wave_sum(a) / f.n[s];
+    float b = 0.f;
+    ms[s] = row_sum(p, f.blocks[s], [&](int i) { b += p[f.wgs[s] + i]; }) / f.n[s];
     mc[s] = wave_sum(b) / f.n[s];
     if (normalize) {
       ms[s] = (ms[s] + 1.f) / 2.f;
@@ -637,121 +598,45 @@ __global__ __launch_bounds__(64) void msssim_finish(const float* __restrict__ sc
   result[row] = (float)out;
 }
 
-// One level of the backward.  grid (cdiv(W, BW), cdiv(H, BH), rows * C).  SSIM_TERM: the SSIM map's gradient times
-// d out / d ssim_level (the last level), else the cs map's times d out / d cs_level.  g_coarse (NULL on the last level): the gradient
-// of the next-coarser level [rows * C, H / 2, W / 2]; a pixel whose 2 x 2 block was dropped by the floor gets nothing from it.
-// SECOND COPY: the moments, the map's partial derivatives and the transposed window passes restate ssim_bwd, for the same reason as
-// msssim_level restates fwd_tile.  A fix to the backward tile has to be made in both places.
+// One level of the backward.  SSIM_TERM: the SSIM map's gradient times d out / d ssim_level (the last level), else the cs map's times
+// d out / d cs_level; g_coarse is NULL on the last level.
 template <bool SSIM_TERM>
 __global__ __launch_bounds__(NT) void msssim_bwd_level(const float* __restrict__ sr, const float* __restrict__ hr,
                                                        const float* __restrict__ g_out, const float* __restrict__ head, int level,
                                                        const float* __restrict__ g_coarse, float* __restrict__ g_sr, int C, int H, int W,
                                                        int taps, float inv_n, int vec_ok) {
-  __shared__ __attribute__((aligned(16))) float px[QH * QW];
-  __shared__ __attribute__((aligned(16))) float py[QH * QW];
-  __shared__ float rf[5][QH][CW];
-  __shared__ float coef[3][CH][CW];
-  float(*ar)[CH][BW] = reinterpret_cast<float(*)[CH][BW]>(&rf[0][0][0]);
-  const int z = blockIdx.z, row = z / C;
-  const int y0 = blockIdx.y * BH, x0 = blockIdx.x * BW;
-  const int Ho = H - taps + 1, Wo = W - taps + 1;
-  const size_t plane = (size_t)z * H * W;
-  load_patch<QH, QW>(sr + plane, px, y0 - HALO, x0 - QX, H, W, vec_ok);
-  load_patch<QH, QW>(hr + plane, py, y0 - HALO, x0 - QX, H, W, vec_ok);
+  const int row = blockIdx.z / C;
   const float* h = head + (size_t)row * MS_HEAD;
-  float C1, C2;
-  ssim_constants(reinterpret_cast<const unsigned*>(h)[2 * MS_LEVELS + level], C1, C2);
-  float g[WIN];
-#pragma unroll
-  for (int k = 0; k < WIN; ++k) g[k] = GN[taps - 1][k];
-  __syncthreads();
+  bwd_tile<SSIM_TERM>(sr, hr, reinterpret_cast<const unsigned*>(h)[2 * MS_LEVELS + level],
+                      (g_out[row] * h[SSIM_TERM ? level : MS_LEVELS + level]) * inv_n, g_coarse, g_sr, H, W, taps, vec_ok);
+}
 
-  for (int i = threadIdx.x; i < QH * CW; i += NT) {
-    const int r = i / CW, cc = i - r * CW;
-    float s[5];
-    row_taps_n(g, px + r * QW + cc + (QX - HALO), py + r * QW + cc + (QX - HALO), s);
-#pragma unroll
-    for (int p = 0; p < 5; ++p) rf[p][r][cc] = s[p];
-  }
-  __syncthreads();
+// the limits of every entry point: rows * C is grid z; in-plane indices are int
+bool too_big(int rows, int C, int H, int W) { return (int64_t)rows * C > 65535 || (int64_t)H * W > 0x7fffffffLL; }
 
-  for (int i = threadIdx.x; i < CH * CW; i += NT) {
-    const int cr = i / CW, cc = i - cr * CW;
-    const int oy = y0 - HALO + cr, ox = x0 - HALO + cc;
-    float a = 0.f, b = 0.f, c = 0.f;
-    if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
-      float m[5];
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], rf[p][cr + k][cc], acc);
-        m[p] = acc;
-      }
-      float r1, r2, B1, B2;
-      const float v = ssim_value(m, C1, C2, r1, r2, B1, B2);
-      {
-#pragma clang fp contract(off)
-        if constexpr (SSIM_TERM) {
-          b = -v / B2;
-          c = (2.f * r1) / B2;
-          const float dm = ((2.f * m[1]) * r2) / B1 - ((2.f * m[0]) * v) / B1;
-          a = (dm - (2.f * m[0]) * b) - m[1] * c;
-        } else {
-          // cs = A2 / B2 does not see mu1 but through s1 and s12; an identical pair gives r2 = 1, c == -2 b and a == 0 exactly
-          b = -r2 / B2;
-          c = 2.f / B2;
-          a = (0.f - (2.f * m[0]) * b) - m[1] * c;
-        }
-      }
-    }
-    coef[0][cr][cc] = a;
-    coef[1][cr][cc] = b;
-    coef[2][cr][cc] = c;
-  }
-  __syncthreads();
-
-  for (int i = threadIdx.x; i < CH * BW; i += NT) {
-    const int cr = i / BW, ix = i - cr * BW;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], coef[p][cr][ix + HALO - k], acc);
-      ar[p][cr][ix] = acc;
-    }
-  }
-  __syncthreads();
-
-  const float scale = (g_out[row] * h[SSIM_TERM ? level : MS_LEVELS + level]) * inv_n;
-  const int H2 = H / 2, W2 = W / 2;
-  for (int i = threadIdx.x; i < BH * BW; i += NT) {
-    const int iy = i / BW, ix = i - iy * BW;
-    const int gy = y0 + iy, gx = x0 + ix;
-    float t[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; ++k) acc = fmaf(g[k], ar[p][iy + HALO - k][ix], acc);
-      t[p] = acc;
-    }
-    if (gy < H && gx < W) {
-#pragma clang fp contract(off)
-      const float x = px[(iy + HALO) * QW + ix + QX], y = py[(iy + HALO) * QW + ix + QX];
-      float v = scale * ((t[0] + (2.f * x) * t[1]) + y * t[2]);
-      if (g_coarse && (gy >> 1) < H2 && (gx >> 1) < W2) v += 0.25f * g_coarse[(size_t)z * H2 * W2 + (size_t)(gy >> 1) * W2 + (gx >> 1)];
-      g_sr[plane + (size_t)gy * W + gx] = v;
-    }
-  }
+int ssim_check(int rows, int C, int H, int W) {
+  if (rows <= 0 || C <= 0 || H < WIN || W < WIN) return SAVFI_E_SHAPE;
+  return too_big(rows, C, H, W) ? SAVFI_E_TOOBIG : SAVFI_OK;
 }
 
 // NULL, then SHAPE, UNSUPPORTED, TOOBIG.  The reference pools once more after the fifth level: 32 is the smallest legal size.
 int msssim_check(int rows, int C, int H, int W, int range_mode) {
   if (rows <= 0 || C <= 0 || H < 32 || W < 32) return SAVFI_E_SHAPE;
   if (range_mode < 0 || range_mode > SAVFI_SSIM_RANGE_FIXED + 3) return SAVFI_E_UNSUPPORTED;
-  if ((int64_t)rows * C > 65535 || (int64_t)H * W > 0x7fffffffLL) return SAVFI_E_TOOBIG;      // ssim_check's limits
-  return SAVFI_OK;
+  return too_big(rows, C, H, W) ? SAVFI_E_TOOBIG : SAVFI_OK;
+}
+
+// float4 loads of both operands' rows: 16-byte aligned planes of a width that is a multiple of four
+int vec4_ok(const float* a, const float* b, int W) { return ((((uintptr_t)a | (uintptr_t)b) & 15u) == 0) && (W % 4 == 0); }
+
+// The range pass over `rows` rows of n elements each -> ext, *eb (max, min) pairs per row
+int launch_range(const float* sr, float* ext, int rows, int64_t n, hipStream_t st, int* eb) {
+  *eb = (int)((n + RANGE_PER_BLOCK - 1) / RANGE_PER_BLOCK);
+  if (*eb > RANGE_MAX_BLOCKS) *eb = RANGE_MAX_BLOCKS;
+  const long long per_block = (((n + *eb - 1) / *eb) + 3) & ~3LL;
+  const int rvec = (((uintptr_t)sr & 15u) == 0) && (rows == 1 || n % 4 == 0);
+  hipLaunchKernelGGL(ssim_range, dim3(*eb, rows), dim3(NT), 0, st, sr, ext, (long long)n, per_block, rvec);
+  return savfi_launch_status();
 }
 
 // Where everything lies in the scratch, in 32-bit words (every region starts on a multiple of four words).  The same for every range mode.
@@ -793,12 +678,6 @@ MsPlan msssim_plan(int rows, int C, int H, int W) {
   return p;
 }
 
-int ssim_check(int rows, int C, int H, int W) {
-  if (rows <= 0 || C <= 0 || H < WIN || W < WIN) return SAVFI_E_SHAPE;
-  if ((int64_t)rows * C > 65535 || (int64_t)H * W > 0x7fffffffLL) return SAVFI_E_TOOBIG;      // grid z; in-plane indices are int
-  return SAVFI_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t savfi_ssim_scratch_floats(int rows, int C, int H, int W) {
@@ -818,21 +697,15 @@ extern "C" int savfi_ssim_loss_f32(const float* sr, const float* hr, float* resu
   }
   const int fixed_cls = range_mode >= SAVFI_SSIM_RANGE_FIXED ? range_mode - SAVFI_SSIM_RANGE_FIXED : -1;
   const int tx = savfi_cdiv(W - HALO, TW), ty = savfi_cdiv(H - HALO, TH);
-  const int64_t n = (int64_t)C * H * W;
-  const int vec_ok = ((((uintptr_t)sr | (uintptr_t)hr) & 15u) == 0) && (W % 4 == 0);
   float* partial = scratch;
   float* ext = scratch + (int64_t)rows * C * tx * ty;
   hipStream_t st = (hipStream_t)stream;
   int eb = 0;
   if (fixed_cls < 0) {
-    eb = (int)((n + RANGE_PER_BLOCK - 1) / RANGE_PER_BLOCK);
-    if (eb > RANGE_MAX_BLOCKS) eb = RANGE_MAX_BLOCKS;
-    const long long per_block = (((n + eb - 1) / eb) + 3) & ~3LL;
-    const int rvec = (((uintptr_t)sr & 15u) == 0) && (rows == 1 || n % 4 == 0);
-    hipLaunchKernelGGL(ssim_range, dim3(eb, rows), dim3(NT), 0, st, sr, ext, (long long)n, per_block, rvec);
-    if (int e = savfi_launch_status()) return e;
+    if (int e = launch_range(sr, ext, rows, (int64_t)C * H * W, st, &eb)) return e;
   }
-  hipLaunchKernelGGL(ssim_fwd, dim3(tx, ty, rows * C), dim3(NT), 0, st, sr, hr, ext, eb, fixed_cls, range_word, partial, C, H, W, vec_ok);
+  hipLaunchKernelGGL(ssim_fwd, dim3(tx, ty, rows * C), dim3(NT), 0, st, sr, hr, ext, eb, fixed_cls, range_word, partial, C, H, W,
+                     vec4_ok(sr, hr, W));
   if (int e = savfi_launch_status()) return e;
   const int64_t n_out = (int64_t)C * (H - HALO) * (W - HALO);
   hipLaunchKernelGGL(ssim_finish, dim3(rows), dim3(64), 0, st, partial, result, C * tx * ty, (float)n_out);
@@ -843,11 +716,10 @@ extern "C" int savfi_ssim_loss_bwd_f32(const float* sr, const float* hr, const f
                                        int rows, int C, int H, int W, void* stream) {
   if (!sr || !hr || !g_loss || !range_word || !g_sr) return SAVFI_E_NULL;
   if (int e = ssim_check(rows, C, H, W)) return e;
-  const int vec_ok = ((((uintptr_t)sr | (uintptr_t)hr) & 15u) == 0) && (W % 4 == 0);
   const int64_t n_out = (int64_t)C * (H - HALO) * (W - HALO);
   const float inv_2n = (float)(1.0 / (2.0 * (double)n_out));
   hipLaunchKernelGGL(ssim_bwd, dim3(savfi_cdiv(W, BW), savfi_cdiv(H, BH), rows * C), dim3(NT), 0, (hipStream_t)stream, sr, hr, g_loss,
-                     range_word, g_sr, C, H, W, inv_2n, vec_ok);
+                     range_word, g_sr, C, H, W, inv_2n, vec4_ok(sr, hr, W));
   return savfi_launch_status();
 }
 
@@ -862,11 +734,11 @@ extern "C" int savfi_psnr_ssim_f32(const float* pred, const float* target, float
   if (!pred || !target || !result || !scratch) return SAVFI_E_NULL;
   if (int e = ssim_check(rows, C, H, W)) return e;
   const int tx = savfi_cdiv(W - HALO, TW), ty = savfi_cdiv(H - HALO, TH);
-  const int vec_ok = ((((uintptr_t)pred | (uintptr_t)target) & 15u) == 0) && (W % 4 == 0);
   float* partial = (float*)scratch;
   unsigned* sq_partial = (unsigned*)(partial + (int64_t)rows * C * tx * ty);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(metric_tile, dim3(tx, ty, rows * C), dim3(NT), 0, st, pred, target, partial, sq_partial, C, H, W, vec_ok);
+  hipLaunchKernelGGL(metric_tile, dim3(tx, ty, rows * C), dim3(NT), 0, st, pred, target, partial, sq_partial, C, H, W,
+                     vec4_ok(pred, target, W));
   if (int e = savfi_launch_status()) return e;
   hipLaunchKernelGGL(metric_finish, dim3(rows), dim3(64), 0, st, partial, sq_partial, result, sq_sum, C * tx * ty,
                      (float)((int64_t)C * (H - HALO) * (W - HALO)), (double)C * H * W);
@@ -892,20 +764,14 @@ extern "C" int savfi_msssim_f32(const float* img1, const float* img2, float* res
   hipStream_t st = (hipStream_t)stream;
   int eb = 0;
   if (fixed_cls < 0) {
-    const int64_t n = (int64_t)C * H * W;
-    eb = (int)((n + RANGE_PER_BLOCK - 1) / RANGE_PER_BLOCK);
-    if (eb > RANGE_MAX_BLOCKS) eb = RANGE_MAX_BLOCKS;
-    const long long per_block = (((n + eb - 1) / eb) + 3) & ~3LL;
-    const int rvec = (((uintptr_t)img1 & 15u) == 0) && (rows == 1 || n % 4 == 0);
-    hipLaunchKernelGGL(ssim_range, dim3(eb, rows), dim3(NT), 0, st, img1, base + p.ext[0], (long long)n, per_block, rvec);
-    if (int e = savfi_launch_status()) return e;
+    if (int e = launch_range(img1, base + p.ext[0], rows, (int64_t)C * H * W, st, &eb)) return e;
   }
   MsFinish f;
   const float* x = img1;
   const float* y = img2;
   for (int s = 0; s < MS_LEVELS; ++s) {
     const bool last = s + 1 == MS_LEVELS;
-    const int vec_ok = ((((uintptr_t)x | (uintptr_t)y) & 15u) == 0) && (p.w[s] % 4 == 0);
+    const int vec_ok = vec4_ok(x, y, p.w[s]);
     float* o1 = last ? nullptr : base + p.img1[s + 1];
     float* o2 = last ? nullptr : base + p.img2[s + 1];
     float* eo = last ? nullptr : base + p.ext[s + 1];
@@ -947,7 +813,7 @@ extern "C" int savfi_msssim_bwd_f32(const float* img1, const float* img2, const 
     const float* y = s ? base + p.img2[s] : img2;
     float* gx = s ? base + p.grad[s] : g_img1;
     const float* gc = last ? nullptr : base + p.grad[s + 1];
-    const int vec_ok = ((((uintptr_t)x | (uintptr_t)y) & 15u) == 0) && (p.w[s] % 4 == 0);
+    const int vec_ok = vec4_ok(x, y, p.w[s]);
     const float inv_n = (float)(1.0 / (double)((int64_t)C * (p.h[s] - p.taps[s] + 1) * (p.w[s] - p.taps[s] + 1)));
     const dim3 grid(savfi_cdiv(p.w[s], BW), savfi_cdiv(p.h[s], BH), rows * C);
     if (last) {
