@@ -84,7 +84,9 @@ extern "C" {
  * savfi_sepconv_bwd2_f32; then savfi_upsample2x_bwd_form; then, for the Laplacian-pyramid loss term, savfi_laploss_scratch_bytes,
  * savfi_laploss_f32, savfi_laploss_bwd_f32; then, for the census loss term, savfi_census_scratch_bytes, savfi_census_f32,
  * savfi_census_bwd_f32; then, for the second-order terms of the two warps, savfi_voxelwarp_bwd2_f32, savfi_flowwarp_bwd2_f32; then, with
- * the one SepConv route, savfi_sepconv_route, savfi_sepconv_debug_span_bytes. */
+ * the one SepConv route, savfi_sepconv_route, savfi_sepconv_debug_span_bytes; then, for the deep layers' small maps,
+ * savfi_convk_wgrad3_small_plan, savfi_convk_wgrad3_small_route, savfi_convk_wgrad3_small_workspace_floats,
+ * savfi_convk_wgrad3_small_tasks_f32, savfi_convk_wgrad3_small_tasks_bias_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -743,6 +745,26 @@ int savfi_convk_wgrad_tasks_reflect_f32(const float* x, const float* gz, float* 
 int savfi_convk_wgrad_sums_bias(int N, int T, int Ci, int Co, int H, int W, int K, int pad);
 int savfi_convk_wgrad_tasks_bias_f32(const float* x, const float* gz, float* gw, float* gb, float* workspace, int N, int T, int Ci, int Co,
                                      int H, int W, int K, int pad, int reflect, void* stream);
+
+/* The 3 x 3 weight gradient (same contract and arithmetic as savfi_convk_wgrad_tasks_f32, K = 3, pad 0 or 1) for maps of at most 32
+ * output columns (SAVFI_E_UNSUPPORTED beyond): a workgroup keeps a band of rows of both operands in LDS and issues all nine taps of the
+ * band between two barriers (csrc/convk_wgrad.hip, convk_wgrad3_small); added under ABI 24.  With at least one 64 x 64 channel block per
+ * CU the kernel writes gw (and gb) itself: one launch, the workspace query answers 0 and `workspace` may be NULL; otherwise the
+ * (sample, band) list is cut into parts whose blocks savfi_convk_wgrad's reduction adds in a fixed order.  Bit-reproducible.
+ *   savfi_convk_wgrad3_small_plan: the plan, on the host (cus > 0: for that many CUs, needs no device; cus <= 0: the device's).
+ *     out[0] rows of a band, out[1] bands of a map (band b = rows b out[0] .. min(Ho, (b + 1) out[0]) - 1), out[2] bytes of LDS of a
+ *     workgroup, out[3] parts of the (sample, band) list, out[4] 1 = gw and gb written by the kernel itself (exactly when
+ *     out[5] >= cus), out[5] channel blocks T ceil(Co / 64) ceil(Ci / 64), out[6] (sample, band) items of a filter set,
+ *     out[7] 32-pixel K-steps of a band.
+ *   savfi_convk_wgrad3_small_route: 1 where savfi_conv3x3_wgrad_wino_tasks_f32 / _bias_f32 hand their call to this kernel
+ *     (Ci, Co >= 256, at most 32 output columns and 768 output pixels; 0 everywhere in a -DSAVFI_WGRAD_SMALL=0 build). */
+int savfi_convk_wgrad3_small_plan(int N, int T, int Ci, int Co, int H, int W, int pad, int cus, int* out /* [8] */);
+int savfi_convk_wgrad3_small_route(int N, int T, int Ci, int Co, int H, int W, int pad);
+int64_t savfi_convk_wgrad3_small_workspace_floats(int N, int T, int Ci, int Co, int H, int W, int pad);
+int savfi_convk_wgrad3_small_tasks_f32(const float* x, const float* gz, float* gw, float* workspace, int N, int T, int Ci, int Co,
+                                       int H, int W, int pad, void* stream);
+int savfi_convk_wgrad3_small_tasks_bias_f32(const float* x, const float* gz, float* gw, float* gb, float* workspace, int N, int T,
+                                            int Ci, int Co, int H, int W, int pad, void* stream);
 
 /* ----------------------------------------------------------------------------------
  * Channel attention + residual of CAIN's RCAB (model_utils.py:931-953 MetaCALayer, :957-990 MetaRCAB):

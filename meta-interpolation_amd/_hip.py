@@ -137,6 +137,11 @@ _PROTOTYPES = {
     "savfi_convk_wgrad_sums_bias": [c_int] * 8,
     "savfi_convk_wgrad_tasks_bias_f32": [_P, _P, _P, _P, _P] + [c_int] * 9 + [_P],
     "savfi_convk_wgrad_tasks_f32": [_P, _P, _P, _P] + [c_int] * 9 + [_P],
+    "savfi_convk_wgrad3_small_plan": [c_int] * 8 + [POINTER(c_int)],
+    "savfi_convk_wgrad3_small_route": [c_int] * 7,
+    "savfi_convk_wgrad3_small_workspace_floats": [c_int] * 7,
+    "savfi_convk_wgrad3_small_tasks_f32": [_P, _P, _P, _P] + [c_int] * 7 + [_P],
+    "savfi_convk_wgrad3_small_tasks_bias_f32": [_P, _P, _P, _P, _P] + [c_int] * 7 + [_P],
     "savfi_ca_pool_f32": [_P, _P, _P, c_int64, c_int, c_float, _P],
     "savfi_ca_mlp_fwd_f32": [_P] * 7 + [c_int] * 4 + [_P],
     "savfi_ca_mlp_bwd_f32": [_P] * 11 + [c_int] * 4 + [c_float, _P],

@@ -20,6 +20,11 @@
 // taps w, w+4, w+8, ... (own accumulators, no reduction between waves).  Unit of staging = 4 output rows x 32 columns of one
 // sample (gz tile + x tile with its K-1 halo); a workgroup walks a contiguous range of units, keeps its accumulators, and
 // writes ONE partial block; convk_wgrad_reduce adds the partial blocks in a fixed order (no atomics).
+//
+// Three kernels: convk_wgrad_kernel (the above: taps dealt out to the waves; 5x5 / 7x7, and 3x3 below 48 channels or `precise`),
+// convk_wgrad3_ring (3x3, all nine taps per wave on a ring of input rows: the mid layers) and convk_wgrad3_small (3x3 on maps of at most 32
+// columns, a whole band of rows of both operands in LDS: the deep 24x32 / 12x16 layers, reached from csrc/wgrad.hip's Winograd entry
+// points where savfi_convk_wgrad3_small_route says so; -DSAVFI_WGRAD_SMALL=0 switches that route off).
 #include "common.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -624,6 +629,233 @@ __global__ __launch_bounds__(ring::NTHR, 1) void convk_wgrad3_ring(const WgArgs 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// 3 x 3 on SMALL MAPS (at most 32 columns): a whole BAND of rows of both operands in LDS, all nine taps per wave.  The ring kernel's unit is
+// 2 rows x 32 columns behind one barrier and a 3-item start-up per run of rows: on a 12 x 16 map half of every unit is empty and a run is 6
+// units long.  Here a workgroup (8 waves on 64 x 64 channels, a wave on 32 x 16 with nine taps in 72 accumulator registers: the ring kernel's
+// tiles, fragment reads, bias sums and epilogue) stages a band of at most 128 cotangent pixels and the input rows under it (+ the 1-pixel
+// halo) ONCE -- loads, 3-way split, LDS images --, passes one barrier, and issues all K-steps x nine taps of the band with no barrier inside;
+// the next band's loads are in flight meanwhile (48 staging registers), a second barrier guards the restaging.  A K-step is 32 pixels: one row
+// of a 17..32-wide map (GW = 32) or two rows of a map of up to 16 columns (GW = 16; the second row's pixels sit one image row further in the
+// input image, a per-lane constant of the fragment address).  Cells beyond the map are zeros of the cotangent (out-of-range buffer offsets);
+// the input image is written completely, so no stale LDS bits meet those zeros.  Work = (sample, band) items of a filter set in ascending
+// order; with at least one 64 x 64 block per CU a workgroup takes all of them and writes gw and gb itself (one launch, no workspace),
+// otherwise the list is cut into contiguous parts and convk_wgrad_reduce adds the parts' blocks.  Fixed summation order: bit-reproducible.
+// ------------------------------------------------------------------------------------------------------------------
+namespace small {
+constexpr int NTHR = 512, MT = 2;
+constexpr int GCELLS_MAX = 128;                         // cotangent cells of a band (4 K-steps)
+constexpr int GIPT = 2, XIPT = 4;                       // staging items (8 channels of a cell) per thread: 8 x 128 and 8 x 204 over 512 threads
+template <int GW>
+struct Geom {
+  static constexpr int RPK = 32 / GW;                   // rows per K-step
+  static constexpr int BH_MAX = GCELLS_MAX / GW;        // rows of a band
+  static constexpr int XW = GW + 2, XCELLS_MAX = (BH_MAX + 2) * XW;
+  static constexpr int GOCT = ckw_oct(GCELLS_MAX), XOCT = ckw_oct(XCELLS_MAX);
+  static constexpr int GPLANE = 8 * GOCT, XPLANE = 8 * XOCT, XBASE = 3 * GPLANE, LDS = 3 * GPLANE + 3 * XPLANE;
+  static_assert(8 * GCELLS_MAX <= GIPT * NTHR && 8 * XCELLS_MAX <= XIPT * NTHR, "staging items per thread");
+  static_assert(LDS <= 160 * 1024, "one workgroup per CU");
+};
+struct Args {
+  const float* x;       // [N][Ci][H][W]
+  const float* gz;      // [N][Co][Ho][Wo]
+  float* out;           // [splits][T][Co][Ci][9] (splits == 1: may be gw itself)
+  float* bias_out;      // [splits][T][Co] or null
+  int T, Ci, Co, H, W, Ho, Wo, pad;
+  int cobs, cibs, splits, items, items_per_split, nbands, bh, bhp;      // bhp: band rows rounded up to whole K-steps
+};
+}  // namespace small
+
+template <int GW, bool BIAS>
+__global__ __launch_bounds__(small::NTHR, 1) void convk_wgrad3_small(const small::Args a) {
+  using namespace small;
+  using G = Geom<GW>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wv & 1, wn = wv >> 1;
+  const int g = lane >> 4, sl = lane & 15, kq = sl >> 2, c4 = sl & 3;     // transpose-read source lane: pixel kq, channel quad c4
+
+  int b = blockIdx.x;
+  const int split = b % a.splits; b /= a.splits;
+  const int cib = b % a.cibs; b /= a.cibs;
+  const int cob = b % a.cobs;
+  const int t = b / a.cobs;
+  const int co0 = cob * 64, ci0 = cib * 64;
+  const int i_begin = split * a.items_per_split, i_end = min(i_begin + a.items_per_split, a.items);
+  const size_t gplane = (size_t)a.Ho * a.Wo, xplane = (size_t)a.H * a.W;
+  const int gplane_b_ = (int)(gplane * 4), xplane_b_ = (int)(xplane * 4);
+  constexpr int OOB = 0x7fffffff;
+
+  // ---- this thread's staging cells (fixed for the launch): wave o stages octet o of the cotangent (its bias sums meet in the wave) ----
+  const int gcells = a.bhp * GW, xcells = (a.bhp + 2) * G::XW;
+  int g_rel[GIPT], g_dy[GIPT], g_dst[GIPT], x_rel[XIPT], x_dy[XIPT], x_dst[XIPT], x_ch[XIPT];
+#pragma unroll
+  for (int k = 0; k < GIPT; ++k) {
+    const int cell = lane + 64 * k, dy = cell / GW, dx = cell - dy * GW;
+    g_dy[k] = dy;
+    g_dst[k] = cell < gcells ? wv * G::GOCT + cell * 16 : -1;
+    g_rel[k] = (cell < gcells && dy < a.bh && dx < a.Wo && co0 + 8 * wv < a.Co) ? (dy * a.Wo + dx) * 4 + (co0 + 8 * wv) * gplane_b_ : OOB;
+  }
+#pragma unroll
+  for (int k = 0; k < XIPT; ++k) {
+    const int item = tid + NTHR * k, o = item / xcells, cell = item - o * xcells;
+    const int dy = cell / G::XW, dx = cell - dy * G::XW, xx = dx - a.pad;
+    x_dy[k] = dy;
+    x_ch[k] = ci0 + 8 * o;
+    x_dst[k] = o < 8 ? G::XBASE + o * G::XOCT + cell * 16 : -1;
+    x_rel[k] = (o < 8 && dy < a.bh + 2 && xx >= 0 && xx < a.W && ci0 + 8 * o < a.Ci) ? (dy * a.W + xx) * 4 + (ci0 + 8 * o) * xplane_b_ : OOB;
+  }
+  const bool g_full = (a.Co & 7) == 0, x_full = (a.Ci & 7) == 0;
+
+  float sg[GIPT][8], sx[XIPT][8];
+  auto stage_load = [&](int i) {
+    int gplane_b = gplane_b_, xplane_b = xplane_b_;       // (opaque: see the ring kernel)
+    asm volatile("" : "+s"(gplane_b), "+s"(xplane_b));
+    const int band = i % a.nbands, n = (i / a.nbands) * a.T + t;
+    const int y0 = band * a.bh, yx = y0 - a.pad;
+    const i32x4 grs = ckw_rsrc(a.gz + (size_t)n * a.Co * gplane, (unsigned)((size_t)a.Co * gplane * 4));
+    const i32x4 xrs = ckw_rsrc(a.x + (size_t)n * a.Ci * xplane, (unsigned)((size_t)a.Ci * xplane * 4));
+    const int g_org = y0 * a.Wo * 4, x_org = yx * a.W * 4;
+    const bool g_in = y0 + a.bh <= a.Ho, x_in = yx >= 0 && yx + a.bh + 2 <= a.H;
+#pragma unroll
+    for (int k = 0; k < GIPT; ++k) {
+      if (64 * k >= gcells) continue;
+      int voff = g_rel[k] == OOB ? OOB : g_rel[k] + g_org;
+      if (!g_in) voff = y0 + g_dy[k] < a.Ho ? voff : OOB;
+      if (g_full) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sg[k][e] = ckw_raw_buffer_load_f32(grs, voff, e * gplane_b, 0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sg[k][e] = ckw_raw_buffer_load_f32(grs, co0 + 8 * wv + e < a.Co ? voff + e * gplane_b : OOB, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < XIPT; ++k) {
+      if (NTHR * k >= 8 * xcells) continue;
+      int voff = x_rel[k] == OOB ? OOB : x_rel[k] + x_org;
+      if (!x_in) voff = (unsigned)(yx + x_dy[k]) < (unsigned)a.H ? voff : OOB;
+      if (x_full) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sx[k][e] = ckw_raw_buffer_load_f32(xrs, voff, e * xplane_b, 0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sx[k][e] = ckw_raw_buffer_load_f32(xrs, x_ch[k] + e < a.Ci ? voff + e * xplane_b : OOB, 0, 0);
+      }
+    }
+  };
+  float bsum[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) bsum[e] = 0.f;
+  const bool do_bias = BIAS && cib == 0;
+  auto stage_write = [&]() {
+    u32x4 p1, p2, p3;
+#pragma unroll
+    for (int k = 0; k < GIPT; ++k) {
+      if (64 * k >= gcells || g_dst[k] < 0) continue;
+      if (do_bias) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bsum[e] += sg[k][e];
+      }
+      char* dst = smem + g_dst[k];
+      ckw_split8(sg[k], p1, p2, p3);
+      *reinterpret_cast<u32x4*>(dst) = p1;
+      *reinterpret_cast<u32x4*>(dst + G::GPLANE) = p2;
+      *reinterpret_cast<u32x4*>(dst + 2 * G::GPLANE) = p3;
+    }
+#pragma unroll
+    for (int k = 0; k < XIPT; ++k) {
+      if (NTHR * k >= 8 * xcells || x_dst[k] < 0) continue;
+      char* dst = smem + x_dst[k];
+      ckw_split8(sx[k], p1, p2, p3);
+      *reinterpret_cast<u32x4*>(dst) = p1;
+      *reinterpret_cast<u32x4*>(dst + G::XPLANE) = p2;
+      *reinterpret_cast<u32x4*>(dst + 2 * G::XPLANE) = p3;
+    }
+  };
+
+  // ---- fragment addresses (transpose reads): source lane (kq, c4) of 16-lane group g points at pixel 8 g + kq (+ 4) of the K-step;
+  //      in the input image that pixel is cell p (GW = 32) or, on the second row of a two-row step, one image row further ----
+  const int frag_lane = (c4 & 1) * 8;
+  const int pix = 8 * g + kq, xcell = GW == 32 ? pix : (pix >> 4) * G::XW + (pix & 15);
+  int a_addr[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) a_addr[m] = (2 * (MT * wm + m) + (c4 >> 1)) * G::GOCT + pix * 16 + frag_lane;
+  const int b_addr = G::XBASE + (2 * wn + (c4 >> 1)) * G::XOCT + xcell * 16 + frag_lane;
+
+  f32x4 acc[9][MT];
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[tp][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  auto tr_read = [&](int addr, int imm) -> bf16x8 {
+    typedef __attribute__((address_space(3))) bf16x4 lds_b4;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4*)(smem + addr + imm));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4*)(smem + addr + imm + 4 * 16));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+
+  if (i_begin < i_end) stage_load(i_begin);
+  for (int i = i_begin; i < i_end; ++i) {
+    stage_write();                                    // (waits for its loads: issued a band ago)
+    __syncthreads();
+    if (i + 1 < i_end) stage_load(i + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    const int rows = min(a.bh, a.Ho - (i % a.nbands) * a.bh), nks = (rows + G::RPK - 1) / G::RPK;
+    for (int s = 0; s < nks; ++s) {
+      bf16x8 aq[MT][3], bq[2][3];
+      const int ab = s * (32 * 16), bb = b_addr + s * (G::RPK * G::XW * 16);
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) aq[m][p] = tr_read(a_addr[m] + ab, p * G::GPLANE);
+      auto load_b = [&](int tap) {
+        const int ky = tap / 3, kx = tap % 3;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) bq[tap & 1][p] = tr_read(bb, p * G::XPLANE + (ky * G::XW + kx) * 16);
+      };
+      load_b(0);
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        if (tap + 1 < 9) load_b(tap + 1);
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+#pragma unroll
+          for (int m = 0; m < MT; ++m)
+            acc[tap][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[m][PA[q]], bq[tap & 1][PB[q]], acc[tap][m], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    __syncthreads();
+  }
+
+  if (do_bias) {          // wave o holds the sums of its octet's eight channels over this workgroup's bands: lanes meet, lane 0 stores
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float s = wave_sum(bsum[e]);
+      const int co = co0 + 8 * wv + e;
+      if (lane == 0 && co < a.Co) a.bias_out[((size_t)split * a.T + t) * a.Co + co] = s;
+    }
+  }
+
+  // ---- D row 4 g + j = co, D column sl = ci; this lane's nine taps of a (co, ci) pair are contiguous ----
+  float* __restrict__ pout = a.out + ((size_t)split * a.T + t) * a.Co * a.Ci * 9;
+  const int ci = ci0 + 16 * wn + sl;
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int co = co0 + 16 * (MT * wm + m) + 4 * g + j;
+      if (co < a.Co && ci < a.Ci) {
+        float* o = pout + ((size_t)co * a.Ci + ci) * 9;
+#pragma unroll
+        for (int tp = 0; tp < 9; ++tp) o[tp] = acc[tp][m][j];
+      }
+    }
+}
+
 // Sum of the partial blocks in a FIXED order (deterministic): a workgroup = 32 outputs x 8 split groups; thread (output, group)
 // adds the splits k = group (mod 8) in increasing order, the eight group sums meet in LDS and are added in group order.
 __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ partial, float* __restrict__ out, long long n, int splits, unsigned block) {
@@ -770,6 +1002,65 @@ int launch_wgrad3_ring(const WgArgs& a, int blocks, float* bias_partial, hipStre
   return savfi_launch_status();
 }
 
+// The plan of convk_wgrad3_small (host only; `cus` > 0: plan for that many CUs, needs no device).
+struct SmallPlan { int gw, bh, bhp, nbands, items, splits, ips, cobs, cibs, blocks, direct, lds; };
+
+inline int small_plan(SmallPlan& p, int N, int T, int Ci, int Co, int H, int W, int pad, int cus) {
+  if (N <= 0 || T <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0 || N % T != 0 || pad < 0) return SAVFI_E_SHAPE;
+  if (pad > 1) return SAVFI_E_UNSUPPORTED;
+  const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
+  if (Ho <= 0 || Wo <= 0) return SAVFI_E_SHAPE;
+  if (Wo > 32) return SAVFI_E_UNSUPPORTED;
+  if ((int64_t)Ci * H * W >= (1ll << 29) || (int64_t)Co * Ho * Wo >= (1ll << 29)) return SAVFI_E_TOOBIG;
+  p.gw = Wo <= 16 ? 16 : 32;
+  const int rpk = 32 / p.gw, bh_max = small::GCELLS_MAX / p.gw;
+  // bands of equal height, at most 128 cotangent cells each: 12 x 16 = two bands of 6 rows, 24 x 32 = six bands of 4 rows
+  p.nbands = (Ho + bh_max - 1) / bh_max;
+  p.bh = (Ho + p.nbands - 1) / p.nbands;
+  p.nbands = (Ho + p.bh - 1) / p.bh;
+  p.bhp = (p.bh + rpk - 1) / rpk * rpk;
+  // the images are laid out for the largest band of the map width (fixed pitches: every fragment offset is an immediate)
+  p.lds = p.gw == 16 ? small::Geom<16>::LDS : small::Geom<32>::LDS;
+  const int64_t items = (int64_t)(N / T) * p.nbands;
+  p.cobs = (Co + 63) / 64;
+  p.cibs = (Ci + 63) / 64;
+  const int64_t blocks = (int64_t)T * p.cobs * p.cibs;
+  if (items > 0x7fffffffLL || blocks > 0x3fffffffLL) return SAVFI_E_TOOBIG;
+  p.items = (int)items;
+  p.blocks = (int)blocks;
+  if (cus <= 0) cus = savfi_cu_count();
+  // one block per CU or more: every workgroup walks all its items and writes gw (and gb) itself.  Fewer: the item list in contiguous
+  // parts, one round of workgroups (parts x blocks <= CUs); a part costs its items + about half an item of start-up and epilogue, and
+  // every part a pass of the reduction over its block
+  p.direct = blocks >= cus ? 1 : 0;
+  int splits = 1;
+  if (!p.direct) {
+    const int smax = (int)std::min<int64_t>(p.items, cus / blocks);
+    double best = 0.0;
+    for (int sp = 1; sp <= smax; ++sp) {
+      const int ips = (p.items + sp - 1) / sp;
+      if ((p.items + ips - 1) / ips != sp) continue;                   // not a distinct cut
+      const double cost = ips + 0.5 + 0.1 * sp;
+      if (sp == 1 || cost < best) { best = cost; splits = sp; }
+    }
+  }
+  p.ips = (p.items + splits - 1) / splits;
+  p.splits = (p.items + p.ips - 1) / p.ips;
+  return SAVFI_OK;
+}
+
+template <int GW>
+int launch_wgrad3_small(const small::Args& a, int blocks, hipStream_t stream) {
+  using G = small::Geom<GW>;
+  static uint32_t configured = 0, configured_b = 0;
+  const int rc = a.bias_out ? savfi_ensure_dynamic_lds(reinterpret_cast<const void*>(convk_wgrad3_small<GW, true>), G::LDS, configured_b)
+                            : savfi_ensure_dynamic_lds(reinterpret_cast<const void*>(convk_wgrad3_small<GW, false>), G::LDS, configured);
+  if (rc != SAVFI_OK) return rc;
+  if (a.bias_out) hipLaunchKernelGGL((convk_wgrad3_small<GW, true>), dim3(blocks), dim3(small::NTHR), G::LDS, stream, a);
+  else hipLaunchKernelGGL((convk_wgrad3_small<GW, false>), dim3(blocks), dim3(small::NTHR), G::LDS, stream, a);
+  return savfi_launch_status();
+}
+
 template <int KS, int MT, int NT, bool P2 = false, int NG = 1>
 int launch_wgrad(const WgArgs& a, int blocks, hipStream_t stream) {
   using G = WgGeom<KS, MT, NT * NG>;
@@ -854,3 +1145,83 @@ int convk_wgrad_run(const float* x, const float* gz, float* gw, float* gb, float
   return savfi_launch_status();
 }
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------------------------
+// The small-map kernel's entry points (include/savfi_hip.h).
+// ------------------------------------------------------------------------------------------------------------------
+#ifndef SAVFI_WGRAD_SMALL
+#define SAVFI_WGRAD_SMALL 1          // 0 (variant builds): the entry points of csrc/wgrad.hip keep their Winograd kernel everywhere
+#endif
+
+extern "C" int savfi_convk_wgrad3_small_plan(int N, int T, int Ci, int Co, int H, int W, int pad, int cus, int* out) {
+  if (!out) return SAVFI_E_NULL;
+  SmallPlan p;
+  const int rc = small_plan(p, N, T, Ci, Co, H, W, pad, cus);
+  if (rc != SAVFI_OK) return rc;
+  out[0] = p.bh; out[1] = p.nbands; out[2] = p.lds; out[3] = p.splits; out[4] = p.direct; out[5] = p.blocks; out[6] = p.items;
+  out[7] = p.bhp * p.gw / 32;
+  return SAVFI_OK;
+}
+
+extern "C" int savfi_convk_wgrad3_small_route(int N, int T, int Ci, int Co, int H, int W, int pad) {
+  if (!SAVFI_WGRAD_SMALL || pad < 0 || pad > 1 || Ci < 256 || Co < 256) return 0;
+  const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
+  if (Ho <= 0 || Wo <= 0 || Wo > 32 || (int64_t)Ho * Wo > 768) return 0;
+  // Decided per class against the Winograd kernel and its reduces (profiles/wgrad_small_maps_bench.txt; us per call, old -> new, the old
+  // kernel's run-to-run spread below 1 us): N = 8, T = 4: 512 -> 512 @24x32 176 -> 136, @12x16 85 -> 47, 256 -> 256 @24x32 68 -> 55, @12x16
+  // 38 -> 34, 512 <-> 256 @24x32 103 -> 91, @12x16 56 -> 48; N = 4, T = 4 (one sample per filter set): 512 -> 512 @24x32 110 -> 76, @12x16
+  // 70 -> 31, 256 -> 256 @24x32 53 -> 43, 512 -> 256 @24x32 73 -> 61, @12x16 45 -> 40; N = 4, T = 1: 512 -> 512 @24x32 104 -> 84, @12x16
+  // 55 -> 42, 256 -> 256 @24x32 49 -> 42, @12x16 43 -> 28.  The one class that loses: 256 -> 256 @12x16 with one sample per filter set and
+  // T = 4 (29.7 -> 31.0: two bands per workgroup do not pay for the staging start-up) -- less than 384 pixels x 256 x 256 channel pairs
+  // per filter set keep the Winograd kernel.
+  if ((int64_t)(N / (T > 0 ? T : 1)) * Ho * Wo * Ci * Co < (int64_t)384 * 256 * 256) return 0;
+  SmallPlan p;
+  return small_plan(p, N, T, Ci, Co, H, W, pad, 0) == SAVFI_OK ? 1 : 0;
+}
+
+extern "C" int64_t savfi_convk_wgrad3_small_workspace_floats(int N, int T, int Ci, int Co, int H, int W, int pad) {
+  SmallPlan p;
+  const int rc = small_plan(p, N, T, Ci, Co, H, W, pad, 0);
+  if (rc != SAVFI_OK) return rc;
+  return p.direct ? 0 : (int64_t)p.splits * T * Co * ((int64_t)Ci * 9 + 1);     // (+ 1: the bias sums' partial blocks)
+}
+
+namespace {
+int convk_wgrad3_small_run(const float* x, const float* gz, float* gw, float* gb, float* workspace, int N, int T, int Ci, int Co, int H, int W,
+                           int pad, void* stream) {
+  if (!x || !gz || !gw) return SAVFI_E_NULL;
+  SmallPlan p;
+  const int rc = small_plan(p, N, T, Ci, Co, H, W, pad, 0);
+  if (rc != SAVFI_OK) return rc;
+  if (!p.direct && !workspace) return SAVFI_E_NULL;
+  const long long n = (long long)T * Co * Ci * 9;
+  small::Args a;
+  a.x = x; a.gz = gz;
+  a.out = p.direct ? gw : workspace;
+  a.bias_out = !gb ? nullptr : p.direct ? gb : workspace + (size_t)p.splits * n;
+  a.T = T; a.Ci = Ci; a.Co = Co; a.H = H; a.W = W; a.Ho = H + 2 * pad - 2; a.Wo = W + 2 * pad - 2; a.pad = pad;
+  a.cobs = p.cobs; a.cibs = p.cibs; a.splits = p.direct ? 1 : p.splits; a.items = p.items; a.items_per_split = p.direct ? p.items : p.ips;
+  a.nbands = p.nbands; a.bh = p.bh; a.bhp = p.bhp;
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = p.blocks * a.splits;
+  const int lrc = p.gw == 16 ? launch_wgrad3_small<16>(a, blocks, st) : launch_wgrad3_small<32>(a, blocks, st);
+  if (lrc != SAVFI_OK || p.direct) return lrc;
+  const bool v4 = n % 4 == 0 && (((uintptr_t)workspace | (uintptr_t)gw) & 15u) == 0;
+  const long long nb = gb ? (long long)T * Co : 0;
+  const unsigned main_blocks = (unsigned)(v4 ? (n / 4 + 31) / 32 : (n + 31) / 32), bias_blocks = (unsigned)((nb + 31) / 32);
+  if (v4) hipLaunchKernelGGL(convk_wgrad_reduce<true>, dim3(main_blocks + bias_blocks), dim3(256), 0, st, workspace, gw, n, p.splits, main_blocks, a.bias_out, gb, nb);
+  else hipLaunchKernelGGL(convk_wgrad_reduce<false>, dim3(main_blocks + bias_blocks), dim3(256), 0, st, workspace, gw, n, p.splits, main_blocks, a.bias_out, gb, nb);
+  return savfi_launch_status();
+}
+}  // namespace
+
+extern "C" int savfi_convk_wgrad3_small_tasks_f32(const float* x, const float* gz, float* gw, float* workspace, int N, int T, int Ci, int Co,
+                                                  int H, int W, int pad, void* stream) {
+  return convk_wgrad3_small_run(x, gz, gw, nullptr, workspace, N, T, Ci, Co, H, W, pad, stream);
+}
+
+extern "C" int savfi_convk_wgrad3_small_tasks_bias_f32(const float* x, const float* gz, float* gw, float* gb, float* workspace, int N, int T,
+                                                       int Ci, int Co, int H, int W, int pad, void* stream) {
+  if (!gb) return SAVFI_E_NULL;
+  return convk_wgrad3_small_run(x, gz, gw, gb, workspace, N, T, Ci, Co, H, W, pad, stream);
+}

@@ -17,6 +17,7 @@
 // MFMAs against 14 LDS reads (b128 / b64) per row.  The four waves' accumulators are added through LDS in a fixed order, every
 // workgroup writes one partial block, and wgrad_reduce adds the partial blocks in a fixed order (no atomics).
 #include "common.h"
+#include <algorithm>
 
 namespace {
 
@@ -689,7 +690,9 @@ extern "C" int64_t savfi_conv3x3_wgrad_wino_tasks_workspace_floats(int N, int T,
   if (pad != 0 && pad != 1) return SAVFI_E_UNSUPPORTED;
   WWPlan p;
   if (!ww_plan(p, N, T, Ci, Co, H, W, pad)) return SAVFI_E_SHAPE;
-  return p.partial_floats + p.stage2_floats;
+  // (at least what the small-map kernel of csrc/convk_wgrad.hip needs where wino_wgrad_tasks hands the call to it)
+  const int64_t small = savfi_convk_wgrad3_small_route(N, T, Ci, Co, H, W, pad) ? savfi_convk_wgrad3_small_workspace_floats(N, T, Ci, Co, H, W, pad) : 0;
+  return std::max(p.partial_floats + p.stage2_floats, small);
 }
 
 extern "C" int64_t savfi_conv3x3_wgrad_wino_tasks_bias_workspace_floats(int N, int T, int Ci, int Co, int H, int W, int pad) {
@@ -724,6 +727,10 @@ static int wino_wgrad_tasks(const float* x, const float* gz, float* gw, float* g
   if (!x || !gz || !gw || !workspace) return SAVFI_E_NULL;
   if (N <= 0 || T <= 0 || N % T != 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return SAVFI_E_SHAPE;
   if (pad != 0 && pad != 1) return SAVFI_E_UNSUPPORTED;
+  // the deep layers' small maps: one band-staged split-bf16 launch (csrc/convk_wgrad.hip, convk_wgrad3_small) instead of the three below
+  if (savfi_convk_wgrad3_small_route(N, T, Ci, Co, H, W, pad))
+    return gb ? savfi_convk_wgrad3_small_tasks_bias_f32(x, gz, gw, gb, workspace, N, T, Ci, Co, H, W, pad, stream)
+              : savfi_convk_wgrad3_small_tasks_f32(x, gz, gw, workspace, N, T, Ci, Co, H, W, pad, stream);
   WWPlan p;
   if (!ww_plan(p, N, T, Ci, Co, H, W, pad)) return SAVFI_E_SHAPE;
   // a sample below 2^30 bytes: byte offsets plus the out-of-range markers (WW_OOR) stay inside 32 bits
