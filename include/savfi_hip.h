@@ -86,7 +86,8 @@ extern "C" {
  * savfi_census_bwd_f32; then, for the second-order terms of the two warps, savfi_voxelwarp_bwd2_f32, savfi_flowwarp_bwd2_f32; then, with
  * the one SepConv route, savfi_sepconv_route, savfi_sepconv_debug_span_bytes; then, for the deep layers' small maps,
  * savfi_convk_wgrad3_small_plan, savfi_convk_wgrad3_small_route, savfi_convk_wgrad3_small_workspace_floats,
- * savfi_convk_wgrad3_small_tasks_f32, savfi_convk_wgrad3_small_tasks_bias_f32. */
+ * savfi_convk_wgrad3_small_tasks_f32, savfi_convk_wgrad3_small_tasks_bias_f32; then, for the AdaCoF plugin's deformable-tap op,
+ * savfi_adacof_fwd_f32, savfi_adacof_bwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -516,6 +517,38 @@ int64_t savfi_census_scratch_bytes(int rows, int n, int C, int H, int W);
 int savfi_census_f32(const float* sr, const float* hr, float* result, void* scratch, int rows, int n, int C, int H, int W, void* stream);
 int savfi_census_bwd_f32(const float* sr, const float* hr, const float* g_loss, float* g_sr, int rows, int n, int C, int H, int W,
                          void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * AdaCoF's deformable-tap op (adaptive collaboration of flows) and its parameter gradients (csrc/adacof.hip), added under ABI 24.
+ *   x [N, C, Hp, Wp] the frame, padded by the caller: Hp = H + (F - 1) d, Wp = W + (F - 1) d, d = `dilation`; C = 3 or 1
+ *   w, a, b [N, F^2, H, W]: per output pixel and tap t = k F + l (k, l in 0 .. F - 1) a weight, a vertical and a horizontal offset
+ *   out [N, C, H, W], fully overwritten.  For pixel (y, x) and tap t:
+ *     sy = float32(y + k d) + a_t            sx = float32(x + l d) + b_t        (ONE fp32 addition each: the coordinate IS fp32)
+ *     sy <- min(max(sy, -1), Hp)             sx <- min(max(sx, -1), Wp)         (in float, before any conversion to an integer)
+ *     iy = floor(sy), ty = sy - iy           ix = floor(sx), tx = sx - ix
+ *     i0 = clamp(iy, 0, Hp - 1), i1 = clamp(iy + 1, 0, Hp - 1), j0, j1 likewise (border replicate)
+ *     S_c = (1 - ty) ((1 - tx) x[c,i0,j0] + tx x[c,i0,j1]) + ty ((1 - tx) x[c,i1,j0] + tx x[c,i1,j1])
+ *     out[n,c,y,x] = sum_t w_t S_c(t), the taps added in the order t = 0 .. F^2 - 1, product first
+ *   bwd: ONE launch, nothing kept from the forward; g_out [N, C, H, W]; g_w, g_a, g_b [N, F^2, H, W], each fully overwritten, each
+ *   may be NULL ("not wanted"), but not all three:
+ *     g_w[t] = sum_c g_out[c] S_c(t)
+ *     g_a[t] = w_t sum_c g_out[c] ((1 - tx) (x[i1,j0] - x[i0,j0]) + tx (x[i1,j1] - x[i0,j1]))
+ *     g_b[t] = w_t sum_c g_out[c] ((1 - ty) (x[i0,j1] - x[i0,j0]) + ty (x[i1,j1] - x[i1,j0]))        (channels added in order)
+ *   No gradient of x is built.  The float clamp changes no value (a coordinate beyond the border reads the border texel either way)
+ *   and makes +-inf and +-1e30 offsets safe; where both indices of an axis clamp to one texel that offset's gradient is exactly 0.
+ *   A NaN offset gives NaN in that pixel's out, in that tap's g_w and in both offset gradients of that tap, never a read outside x.
+ *   Errors, checked in this order before any launch: SAVFI_E_NULL (an operand, or all three of g_w, g_a, g_b); SAVFI_E_SHAPE (one of
+ *   N, C, H, W, F, dilation <= 0); SAVFI_E_UNSUPPORTED (C not 1 or 3, F even or above 11, dilation above 8, an output pointer equal
+ *   to an operand or to another output, a pointer that is not 4-byte aligned); SAVFI_E_TOOBIG (N F^2 H W or N C Hp Wp >= 2^31).
+ *   One launch each of 256-thread workgroups, one per tile of 4 rows x 64 columns per sample, one pixel per thread walking the F^2
+ *   taps: the 3 F^2 parameter planes stream coalesced and non-temporally, the frame gathers go through the cache.  fp32, every
+ *   operation rounded on its own (no contraction, no reassociation).  No atomics, no cleared memory, no host read: capturable and
+ *   bit-reproducible.  All global accesses are scalar 4-byte ones: operands 4 bytes off a 16-byte boundary give the same bits.
+ * ---------------------------------------------------------------------------------- */
+int savfi_adacof_fwd_f32(const float* x, const float* w, const float* a, const float* b, float* out, int N, int C, int H, int W, int F,
+                         int dilation, void* stream);
+int savfi_adacof_bwd_f32(const float* x, const float* w, const float* a, const float* b, const float* g_out, float* g_w, float* g_a,
+                         float* g_b, int N, int C, int H, int W, int F, int dilation, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:

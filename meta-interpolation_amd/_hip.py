@@ -94,6 +94,8 @@ _PROTOTYPES = {
     "savfi_census_scratch_bytes": [c_int, c_int, c_int, c_int, c_int],
     "savfi_census_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_census_bwd_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "savfi_adacof_fwd_f32": [_P] * 5 + [c_int] * 6 + [_P],
+    "savfi_adacof_bwd_f32": [_P] * 8 + [c_int] * 6 + [_P],
     "savfi_upsample2x_fwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_bwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_workspace_floats": [c_int] * 7,

@@ -26,6 +26,8 @@ Additions for the MI355X build (all optional, all default to the reference behav
                                kernel each); default 0: the VoxelFlow tail is composed from ATen ops in second-order passes and the pixel-flow
                                warp's backward is once differentiable (--second_order raises on those two models).  Has effect only in
                                second-order passes
+  --adacof_kernel_size F       --model adacof: F x F taps per output pixel, each with a weight and a learned 2-D offset (odd, 1 to 11; default 5)
+  --adacof_dilation D          --model adacof: spacing of the taps' base positions (1 to 8; default 1); the op reads a frame padded by (F - 1) D / 2
   --loss ...+w*MSSSIM          a term the reference's Loss has no branch for: 1 - msssim(sr, hr, normalize=True) on the fused multi-scale kernels
   --loss ...+w*Lap             another one: the Laplacian-pyramid L1 (five levels, 5-tap binomial window, reflected borders, low-pass residual last,
                                sum_s 2^s sum |b_s| / n_0) on the fused kernels of csrc/laploss.hip; frames of 17 x 17 or more
@@ -68,12 +70,13 @@ _FLAGS = {
         ('fuse_support_pairs', int, 1), ('fuse_conv_act', int, 1), ('graph_inner_loop', int, -1), ('sepconv_window', int, 1),
         ('task_streams', int, -1), ('wgrad_overlap', int, 0), ('task_batch', int, 8), ('lazy_logging', int, 1),
         ('dain_task_modes', int, 0), ('eval_msssim', int, 0), ('sepconv_second_order', int, 0),
-        ('warp_second_order', int, 0),
+        ('warp_second_order', int, 0), ('adacof_kernel_size', int, 5), ('adacof_dilation', int, 1),
         ('synthetic', 'flag', False),
     ],
 }
 
-_CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1], 'sepconv_second_order': [0, 1], 'warp_second_order': [0, 1]}
+_CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1], 'sepconv_second_order': [0, 1], 'warp_second_order': [0, 1],
+            'adacof_kernel_size': [1, 3, 5, 7, 9, 11], 'adacof_dilation': list(range(1, 9))}
 
 
 def build_parser():

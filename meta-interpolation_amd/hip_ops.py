@@ -1225,6 +1225,114 @@ def census_loss_per_sample(sr, hr):
     return _CensusLoss.apply(sr, hr, False)
 
 
+# --------------------------------------------------------------------------------------------
+# AdaCoF's deformable-tap op, the tail of --model adacof   (no counterpart in the reference; definition: include/savfi_hip.h)
+# --------------------------------------------------------------------------------------------
+def adacof_bytes(x, w, grads=0):
+    """HBM bytes of one launch if every operand is read / written exactly once: the frame, the three parameter stacks, the output (or
+    its cotangent) and `grads` gradient stacks"""
+    N, C = x.shape[0], x.shape[1]
+    return 4 * (x.numel() + (3 + grads) * w.numel() + N * C * w.shape[2] * w.shape[3])
+
+
+class _AdaCoF(torch.autograd.Function):
+    """x [N,C,Hp,Wp] (no gradient), w, a, b [N,F^2,H,W] -> [N,C,H,W]: one launch forward, one launch backward for whichever of the
+    three parameter gradients are needed; capturable; deterministic."""
+
+    @staticmethod
+    def forward(ctx, x, w, a, b, F, dilation):
+        _hip.require_cuda(x, w, a, b)
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("adacof: the frame requires grad, and the fused op builds no frame gradient (it would be dropped "
+                                      "silently); hip_ops.adacof_composed differentiates it")
+        N, C = x.shape[0], x.shape[1]
+        H, W = w.shape[2], w.shape[3]
+        out = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device)
+        _hip.call("adacof_fwd", "savfi_adacof_fwd_f32", x, w, a, b, out, N, C, H, W, F, dilation, nbytes=adacof_bytes(x, w))
+        ctx.geom = (N, C, H, W, F, dilation)
+        ctx.save_for_backward(x, w, a, b)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w, a, b = ctx.saved_tensors
+        needs = ctx.needs_input_grad[1:4]
+        if not any(needs):
+            return None, None, None, None, None, None
+        g = g.contiguous()
+        _hip.require_cuda(g)
+        gw, ga, gb = (torch.empty_like(w) if need else None for need in needs)
+        _hip.call("adacof_bwd", "savfi_adacof_bwd_f32", x, w, a, b, g, gw, ga, gb, *ctx.geom, nbytes=adacof_bytes(x, w, sum(needs)))
+        return None, gw, ga, gb, None, None
+
+
+def _adacof_args(x, w, a, b, dilation, what):
+    """-> F, after the checks of the C entry that shapes decide (a ValueError names the argument instead of an error code)"""
+    if x.dim() != 4 or w.dim() != 4 or a.shape != w.shape or b.shape != w.shape:
+        raise ValueError("%s needs a frame [N,C,Hp,Wp] and three [N,F*F,H,W] tensors of one shape, got %s, %s, %s, %s"
+                         % (what, tuple(x.shape), tuple(w.shape), tuple(a.shape), tuple(b.shape)))
+    F = int(round(w.shape[1] ** 0.5))
+    if F * F != w.shape[1] or F % 2 == 0 or F > 11:
+        raise ValueError("%s needs F * F taps with F odd and at most 11, got %d planes" % (what, w.shape[1]))
+    dilation = int(dilation)
+    if not 1 <= dilation <= 8:
+        raise ValueError("%s needs a dilation of 1 to 8, got %d" % (what, dilation))
+    if x.shape[1] not in (1, 3):
+        raise ValueError("%s needs 3 channels or 1, got %s" % (what, tuple(x.shape)))
+    N, _, H, W = w.shape
+    rim = (F - 1) * dilation
+    if x.shape[0] != N or x.shape[2] != H + rim or x.shape[3] != W + rim:
+        raise ValueError("%s needs the frame padded by (F - 1) * dilation = %d in all: [%d,C,%d,%d], got %s"
+                         % (what, rim, N, H + rim, W + rim, tuple(x.shape)))
+    return F
+
+
+def adacof_composed(x, w, a, b, dilation=1):
+    """The definition of adacof() from differentiable torch ops, on any device and in any floating dtype: what second-order passes
+    (set_double_backward(True)), CPU tensors and non-fp32 tensors take.  The coordinate is formed in the tensors' dtype (one addition to
+    an exact integer), clamped to [-1, size] before the cell is taken; differentiable to any order in w, a, b and x."""
+    F = _adacof_args(x, w, a, b, dilation, "adacof_composed")
+    dilation = int(dilation)
+    N, C, Hp, Wp = x.shape
+    _, F2, H, W = w.shape
+    tap = torch.arange(F2, device=x.device)
+    base_y = (torch.arange(H, device=x.device).view(1, 1, H, 1) + (tap // F * dilation).view(1, F2, 1, 1)).to(a.dtype)
+    base_x = (torch.arange(W, device=x.device).view(1, 1, 1, W) + (tap % F * dilation).view(1, F2, 1, 1)).to(b.dtype)
+
+    def axis(s, size):
+        s = s.clamp(-1, size)                                          # NaN passes
+        cell = s.detach().floor()
+        t = s - cell
+        i = torch.nan_to_num(cell, nan=-1.0).long()
+        return i.clamp(0, size - 1), (i + 1).clamp(0, size - 1), t.unsqueeze(1)
+
+    i0, i1, ty = axis(base_y + a, Hp)
+    j0, j1, tx = axis(base_x + b, Wp)
+    flat = x.reshape(N, C, Hp * Wp)
+
+    def texel(i, j):
+        return flat.gather(2, (i * Wp + j).reshape(N, 1, -1).expand(N, C, -1)).reshape(N, C, F2, H, W)
+
+    top = (1 - tx) * texel(i0, j0) + tx * texel(i0, j1)
+    bot = (1 - tx) * texel(i1, j0) + tx * texel(i1, j1)
+    return (w.unsqueeze(1) * ((1 - ty) * top + ty * bot)).sum(2)
+
+
+def adacof(x, w, a, b, dilation=1):
+    """AdaCoF's op: x [N,C,Hp,Wp] the frame padded by (F - 1) * dilation in all, w / a / b [N,F*F,H,W] a weight, a vertical and a horizontal
+    offset per output pixel and tap -> [N,C,H,W], out = sum_t w_t * bilinear(x, (y + k d + a_t, x + l d + b_t)) with border replicate
+    (include/savfi_hip.h).  fp32 device tensors take the fused kernels: one launch forward, one backward, gradients for w, a, b only (a
+    frame that requires grad is refused).  Second-order passes, CPU tensors and other dtypes take adacof_composed."""
+    F = _adacof_args(x, w, a, b, dilation, "adacof")
+    tensors = (x, w, a, b)
+    if double_backward() or not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return adacof_composed(x, w, a, b, dilation)
+    x, w, a, b = (t.contiguous() for t in tensors)
+    _hip.require_cuda(x, w, a, b)
+    return _AdaCoF.apply(x, w, a, b, F, int(dilation))
+
+
 def frames_to_u8(x):
     """x [N,C,H,W] (or [C,H,W], [H,W]) in unit range, C = 1 or 3 -> uint8 [N,H,W,C] ([H,W,C], [H,W]) on the device, quantised as
     utils.save_image does (the metric's device function): a frame leaves the device as bytes."""

@@ -4,7 +4,11 @@ Under torch.distributed.run (one process per GPU) the meta-batch is sharded acro
 RCCL all-reduce of outer gradients per iteration; with a single process it is the sequential loop.
 
 --model dain adapts its tasks one by one in the eager loop unless --dain_task_modes 1 is given: then --task_batch, --graph_inner_loop and
---task_streams mean for it what they mean for the other plugins (config.py; not with --second_order, not on the host)."""
+--task_streams mean for it what they mean for the other plugins (config.py; not with --second_order, not on the host).
+
+--model adacof (an addition: the reference has no such plugin) is the SepConv U-Net with AdaCoF's deformable-tap tail on fused HIP kernels
+(adacof/model.py; --adacof_kernel_size, --adacof_dilation); every task mode of the SepConv plugin applies, --second_order and the host take
+the op composed from torch ops."""
 from .config import get_args
 from .data import MetaLearningSystemDataLoader
 from .experiment_builder import ExperimentBuilder

@@ -77,8 +77,14 @@ def _build_dain(args, resume):
     return MetaDAIN(resume=resume)
 
 
+def _build_adacof(args, resume):
+    from .adacof.model import MetaAdaCoF
+    return MetaAdaCoF(kernel_size=int(getattr(args, 'adacof_kernel_size', 5)), dilation=int(getattr(args, 'adacof_dilation', 1)),
+                      resume=resume)
+
+
 MODEL_REGISTRY = {'sepconv': _build_sepconv, 'cain': _build_cain, 'voxelflow': _build_voxelflow, 'rrin': _build_rrin,
-                  'superslomo': _build_superslomo, 'dain': _build_dain}
+                  'superslomo': _build_superslomo, 'dain': _build_dain, 'adacof': _build_adacof}
 
 
 def register_model(name, factory):

@@ -27,9 +27,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import hip_ops
-from ..hip_ops import Upsample2x, upsample_bilinear2x_window, upsample_window_sources
-from ..model_utils import MetaConv2dLayer, MetaSequential, as_view, fuse_conv_act, fuse_conv_chain, own_params_const, zero_grad_params
+from .. import hip_ops, kernel_unet
+from ..hip_ops import upsample_bilinear2x_window, upsample_window_sources
+from ..model_utils import as_view, fuse_conv_act, fuse_conv_chain, own_params_const, zero_grad_params
 from .sepconv_op.sepconv import FunctionSepconv, FunctionSepconvPair, FunctionSepconvTwice, frames8_supported
 
 TAPS_UNIT16 = True        # A/B (module attributes, no environment variable): False = planar taps / tap gradients
@@ -42,34 +42,11 @@ FILTER_TAPS = 51
 HALF = FILTER_TAPS // 2  # 25
 
 
-def _conv(cin, cout):
-    return MetaConv2dLayer(in_channels=cin, out_channels=cout, kernel_size=3, stride=1, padding=1)
-
-
-def _basic(cin, cout):
-    return MetaSequential(_conv(cin, cout), nn.ReLU(inplace=False),
-                          _conv(cout, cout), nn.ReLU(inplace=False),
-                          _conv(cout, cout), nn.ReLU(inplace=False))
-
-
-def _upsample(ch):
-    return MetaSequential(Upsample2x(align_corners=True), _conv(ch, ch), nn.ReLU(inplace=False))
-
-
 def _subnet():
-    return MetaSequential(_conv(64, 64), nn.ReLU(inplace=False),
-                          _conv(64, 64), nn.ReLU(inplace=False),
-                          _conv(64, FILTER_TAPS), nn.ReLU(inplace=False),
-                          Upsample2x(align_corners=True),
-                          _conv(FILTER_TAPS, FILTER_TAPS))
+    return kernel_unet.head(FILTER_TAPS)
 
 
 _FRAME_TLS = threading.local()       # MetaNetwork._prepared_frames: per thread, per network
-
-_ENCODER = [("moduleConv1", 6, 32), ("moduleConv2", 32, 64), ("moduleConv3", 64, 128),
-            ("moduleConv4", 128, 256), ("moduleConv5", 256, 512)]
-_DECODER = [("moduleDeconv5", 512, 512), ("moduleDeconv4", 512, 256), ("moduleDeconv3", 256, 128),
-            ("moduleDeconv2", 128, 64)]
 
 
 class MetaNetwork(nn.Module):
@@ -82,12 +59,7 @@ class MetaNetwork(nn.Module):
         # op is FunctionSepconvTwice, whose backward carries a graph; False: FunctionSepconv, which drops those terms like the reference
         self.sepconv_second_order = False
         self._windows = {}
-        for i, (name, cin, cout) in enumerate(_ENCODER, start=1):
-            setattr(self, name, _basic(cin, cout))
-            setattr(self, "modulePool%d" % i, hip_ops.AvgPool2x2())
-        for name, cin, cout in _DECODER:
-            setattr(self, name, _basic(cin, cout))
-            setattr(self, name.replace("Deconv", "Upsample"), _upsample(cout))
+        kernel_unet.build(self)       # moduleConv1..5 / modulePool1..5, moduleDeconv5..2 / moduleUpsample5..2
         self.moduleVertical1 = _subnet()
         self.moduleVertical2 = _subnet()
         self.moduleHorizontal1 = _subnet()
@@ -114,27 +86,7 @@ class MetaNetwork(nn.Module):
         pv = as_view(params)
         fast = (lambda n: None) if pv is None else pv.sub
 
-        x = prep['x']
-        skips = []
-        for i, (name, _, _) in enumerate(_ENCODER, start=1):
-            # the block's activated output feeds the pooling and a skip connection: one op with one element-wise pass in backward (the
-            # pooling's adjoint + the sum of the two cotangents + the block's last ReLU derivative, which the block leaves to it)
-            # (where the block's last layer runs on the F(4x4) kernel, its output stage has stored the pooled map already: POOL_EPILOGUE)
-            if x.is_cuda:
-                res = getattr(self, name)(x, fast(name), defer_last=True, pool_last=POOL_EPILOGUE)
-                x, slope, pooled = res if POOL_EPILOGUE else res + (None,)
-                x, skip = (pooled, x) if pooled is not None else hip_ops.avg_pool2x2_and_skip(x, slope)
-            else:
-                x, slope = getattr(self, name)(x, fast(name), defer_last=True)
-                assert slope is None
-                x, skip = getattr(self, "modulePool%d" % i)(x), x
-            skips.append(skip)
-        for name, _, _ in _DECODER:
-            # (the block's last ReLU has one consumer, the bilinear x2 of its Upsample: its derivative is left to that op's adjoint)
-            x, slope = getattr(self, name)(x, fast(name), defer_last=True)
-            x = getattr(self, name.replace("Deconv", "Upsample"))(x, in_slope=slope)   # own parameters, as the reference
-            x = x + skips.pop()
-        combine = x  # [N,64,ph/2,pw/2]
+        combine = kernel_unet.run(self, prep['x'], fast, POOL_EPILOGUE)  # [N,64,ph/2,pw/2]
 
         if self.windowed and combine.is_cuda:
             return self._windowed_tail(tensorFirst, tensorSecond, combine, height, width, ph, pw, prep)

@@ -13,10 +13,18 @@ import torch
 
 # Xavier-uniform bound multiplier per plugin: keeps un-normalised random nets at O(1) outputs
 # (raw Xavier makes CAIN's 127-conv stack blow up to L1 ~ 20; SepConv's separable taps need 1.2x to leave ~0).
-_GAIN = {'sepconv': 1.2, 'cain': 0.5, 'voxelflow': 1.0, 'rrin': 1.0, 'superslomo': 1.68}
+_GAIN = {'sepconv': 1.2, 'cain': 0.5, 'voxelflow': 1.0, 'rrin': 1.0, 'superslomo': 1.68, 'adacof': 1.2}
 # per sub-network overrides (name prefix): RRIN's flow nets need > 1 to produce flows of a sizeable fraction of a pixel,
 # its `final` residual net < 1 so that the clamp(0, 1) at the end does not saturate
-_GAIN_PREFIX = {'rrin': {'Flow_L.': 1.3, 'refine_flow.': 1.3, 'final.': 0.85}}
+_GAIN_PREFIX = {'rrin': {'Flow_L.': 1.3, 'refine_flow.': 1.3, 'final.': 0.85},
+                # AdaCoF: the SepConv backbone's 1.2; the four offset heads 1.8, so that seeded offsets are a sizeable fraction of a pixel
+                # up to a few pixels and both the in-cell and the cell-crossing path of the op run.  Measured on the seeded 128 x 128
+                # septuplet (F = 5): mean |offset| 0.35 px, std 0.48, largest 2.6 px, 24 % beyond half a pixel, 4.8 % beyond one, half of
+                # them negative (a negative offset leaves its base cell at once); predictions stay in [0.02, 1.0] (a softmax-weighted
+                # mean of texels cannot leave the frame's range).  1.6 gives mean 0.22 / largest 1.6, 2.0 mean 0.53 / largest 3.9: the
+                # middle one is taken -- no larger than the two paths need: every cell an offset crosses is a kink an inner step can move
+                # over, which is what makes the VoxelFlow default recipe chaotic
+                'adacof': {'moduleAlpha': 1.8, 'moduleBeta': 1.8}}
 # Super SloMo works on mean-subtracted frames (data/vimeo_septuplet.py:31-33; meta_learning_system.py:71-73 undoes it)
 SUPERSLOMO_MEAN = (0.429, 0.431, 0.397)
 
