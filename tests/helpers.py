@@ -1,6 +1,9 @@
 """Shared test helpers (CPU side): build oracle inputs from the seeded recipe, read golden fixtures."""
 import ast
+import collections
 import contextlib
+import ctypes
+import functools
 import os
 
 import numpy as np
@@ -125,6 +128,174 @@ def record_launches():
         yield rec
     finally:
         _hip.launch, _hip.check = launch, check
+
+
+GUARD_PAD = 1024          # floats of canary on either side of a storage under guarded_calls(): 4096 bytes, a multiple of 512
+
+
+class GuardedCalls:
+    """What guarded_calls() did: `guarded` counts the symbols it wrapped (those that ran between canaries; a call passed through
+    during a stream capture is not counted)."""
+
+    def __init__(self):
+        self.guarded = collections.Counter()
+
+
+def _capturing(device):
+    return device != "cpu" and torch.cuda.is_current_stream_capturing()
+
+
+def _storage_bytes(storage):
+    """The whole untyped storage as a 1-D uint8 tensor (a view, no copy)."""
+    return torch.zeros(0, dtype=torch.uint8, device=storage.device).set_(storage)
+
+
+class _GuardedCopy:
+    """One storage between two canary regions of `pad` floats, at the storage's own alignment modulo 512 bytes."""
+    ALIGN = 512
+
+    def __init__(self, storage, pad, arg):
+        self.orig, self.base, self.nbytes, self.arg, self.padb = _storage_bytes(storage), storage.data_ptr(), storage.nbytes(), arg, 4 * pad
+        words = 2 * pad + (self.nbytes + 3) // 4 + self.ALIGN // 4
+        self.buf = torch.full((words,), CANARY, dtype=torch.float32, device=storage.device).view(torch.uint8)
+        self.lead = self.padb + (self.base - self.buf.data_ptr() - self.padb) % self.ALIGN
+        self.copy_base = self.buf.data_ptr() + self.lead
+        self.buf[self.lead:self.lead + self.nbytes].copy_(self.orig)
+
+    def translate(self, ptr):
+        """`ptr` inside the storage -> the same offset in the copy; None when it lies elsewhere."""
+        return self.copy_base + (ptr - self.base) if self.base <= ptr < self.base + self.nbytes else None
+
+    def touched(self):
+        """(side, byte offset) of the first changed canary word, or None.  The offset counts from the start of the storage's bytes
+        (negative before it, >= its size after it), rounded down to the word."""
+        for side, start, stop in (("before", 0, self.lead), ("after", self.lead + self.nbytes, self.buf.numel())):
+            want = torch.full(((stop - start) // 4 + 2,), CANARY, dtype=torch.float32, device=self.buf.device).view(torch.uint8)
+            bad = self.buf[start:stop] != want[start % 4:start % 4 + stop - start]
+            if bool(bad.any()):
+                first = start + int(bad.to(torch.uint8).argmax())
+                return side, (first - first % 4) - self.lead
+        return None
+
+    def copy_back(self):
+        self.orig.copy_(self.buf[self.lead:self.lead + self.nbytes])
+
+
+@contextlib.contextmanager
+def guarded_calls(device="cuda", pad=GUARD_PAD):
+    """Run every _hip.call of the block on canary-padded copies of its tensors' storages: per distinct untyped storage behind a tensor
+    argument, `pad` floats of CANARY, the storage's bytes, `pad` floats of CANARY.  Tensors go as the same offset into their storage's
+    copy, and so do raw pointers that lie inside such a storage (integer arguments -- the raw pointer sums -- and the entries of
+    ptr_array host arrays; a pointer into no tensor argument's storage stays as it is).  After the launch both canary regions of every
+    copy are checked and every storage is copied back, so the caller's tensors hold what the kernel wrote.  A touched canary raises
+    an AssertionError naming the symbol, the index of the (first) argument of that storage, the side and the byte offset of the first
+    changed word.  The device is synchronised around the copies (side streams exist).  `pad` = 1024 floats is a multiple of 512 bytes
+    and the copy sits at the storage's offset modulo 512, so alignment-selected kernel paths do not change.
+
+    The limit: the guard is per STORAGE.  A write through one view into the neighbouring slice of the same storage (a channel slice, an
+    interleaved tap plane) stays inside the copy and is not reported; the slice tests of the ops that write into slices cover that.
+    A raw pointer is translated when it lies in [start, start + size) of a substituted storage: one that equals the end (an end pointer,
+    a zero-length tail) stays where it was, as does the pointer of a tensor whose storage has no bytes.
+    While the current stream is capturing a graph the call is passed through untouched.  _hip.call comes back on exit."""
+    from meta_interpolation_amd import _hip
+    rec, call = GuardedCalls(), _hip.call
+
+    def sync():
+        if device != "cpu":
+            torch.cuda.synchronize()
+
+    def guarded(name, symbol, *args, nbytes=0, flops=0, stream=None):
+        if _capturing(device):
+            return call(name, symbol, *args, nbytes=nbytes, flops=flops, stream=stream)
+        sync()
+        copies = {}
+        for i, a in enumerate(args):
+            if isinstance(a, torch.Tensor):
+                st = a.untyped_storage()
+                if st.nbytes() and st.data_ptr() not in copies:
+                    copies[st.data_ptr()] = _GuardedCopy(st, pad, i)
+
+        def moved(ptr):
+            for c in copies.values():
+                new = c.translate(ptr)
+                if new is not None:
+                    return new
+            return ptr
+
+        argv = []
+        for a in args:
+            if isinstance(a, torch.Tensor):
+                argv.append(moved(a.data_ptr()))
+            elif isinstance(a, int) and not isinstance(a, bool):
+                argv.append(moved(a))
+            elif isinstance(a, ctypes.Array) and a._type_ is ctypes.c_void_p:
+                arr = type(a)()
+                for k, p in enumerate(a):
+                    arr[k] = None if p is None else moved(p)
+                argv.append(arr)
+            else:
+                argv.append(a)
+        sync()
+        rec.guarded[symbol] += 1
+        call(name, symbol, *argv, nbytes=nbytes, flops=flops, stream=stream)
+        sync()
+        hits = [(c, c.touched()) for c in copies.values()]
+        for c in copies.values():
+            c.copy_back()
+        sync()
+        for c, hit in hits:
+            assert hit is None, "%s: argument %d: wrote %s its storage, first changed word at byte offset %d (storage of %d bytes)" % (
+                symbol, c.arg, hit[0], hit[1], c.nbytes)
+
+    _hip.call = guarded
+    try:
+        yield rec
+    finally:
+        _hip.call = call
+
+
+class PoisonedEmpties:
+    """What poisoned_empties() did: `filled` counts the allocations it filled."""
+
+    def __init__(self):
+        self.filled = 0
+
+
+def integer_poison(dtype):
+    return torch.iinfo(dtype).max
+
+
+@contextlib.contextmanager
+def poisoned_empties():
+    """torch.empty, torch.empty_like and torch.Tensor.new_empty return filled memory while the block runs: NaN in a floating dtype, the
+    dtype's maximum in an integer one (bool is left alone), so an element a kernel never writes, or a workspace it reads first, shows in
+    the result whatever the allocator's block held before.  Nothing is filled while the current stream is capturing.  The originals come
+    back on exit."""
+    rec = PoisonedEmpties()
+    empty, empty_like, new_empty = torch.empty, torch.empty_like, torch.Tensor.new_empty
+
+    def poison(t):
+        if not isinstance(t, torch.Tensor) or t.dtype == torch.bool or t.numel() == 0 or (t.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return t
+        with torch.no_grad():
+            if t.dtype.is_floating_point or t.dtype.is_complex:
+                t.fill_(float('nan'))
+            else:
+                t.fill_(integer_poison(t.dtype))
+        rec.filled += 1
+        return t
+
+    def wrap(fn):
+        @functools.wraps(fn)
+        def filled(*args, **kwargs):
+            return poison(fn(*args, **kwargs))
+        return filled
+
+    torch.empty, torch.empty_like, torch.Tensor.new_empty = wrap(empty), wrap(empty_like), wrap(new_empty)
+    try:
+        yield rec
+    finally:
+        torch.empty, torch.empty_like, torch.Tensor.new_empty = empty, empty_like, new_empty
 
 
 def build_system(model, overrides, fuse=1, device="cuda"):

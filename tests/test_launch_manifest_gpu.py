@@ -7,7 +7,11 @@ moves one of them, renames a launch, reorders two or checks a code under another
 
 The fixture was recorded ONCE, by `python -m tests.test_launch_manifest_gpu <path>` on an MI355X, from the commit before the op layer
 moved to _hip.call (this file and the recorder of tests/helpers.py placed on that tree).  It is not regenerated from the code under test:
-a case that legitimately changes gets its entry edited by hand, with the reason in the commit.
+a case that legitimately changes gets its entry edited by hand, with the reason in the commit.  The two adacof entries were written by
+hand in that way (the op came after the recording): adacof_bytes of the case's shapes, each operand once.
+
+Every case returns the tensors it produced (outputs, gradients, buffers updated in place) as a flat list: this file drops them,
+tests/test_launch_guards_gpu.py compares two runs of each case through them.
 
 Shapes: the warps, SepConv and the loss terms at the smallest size that reaches each path; every other op at the smallest shape its own
 GPU test uses (the convolution routes: the cases of tests/test_conv_dispatch_gpu.py).  Module knobs stay at their defaults except where a
@@ -36,6 +40,20 @@ def _gen(seed=0):
     return torch.Generator(device=DEV).manual_seed(seed)
 
 
+def _flat(*results):
+    """Every tensor in `results` (tensors, None, scalars, nested lists / tuples / dicts of them), detached, in order: what a case
+    returns, so that a caller can compare two runs of it."""
+    out = []
+    for r in results:
+        if isinstance(r, torch.Tensor):
+            out.append(r.detach())
+        elif isinstance(r, dict):
+            out += _flat(*r.values())
+        elif isinstance(r, (list, tuple)):
+            out += _flat(*r)
+    return out
+
+
 def _randn(g, *shape, grad=False):
     return torch.randn(shape, device=DEV, generator=g).requires_grad_(grad)
 
@@ -61,7 +79,7 @@ def _warp_once(fn, a_shape, b_shape, a_grad):
     g = _gen(1)
     a, b = _randn(g, *a_shape, grad=a_grad), _randn(g, *b_shape, grad=True)
     out = fn(a, b)
-    torch.autograd.grad(out, [a, b] if a_grad else [b], _randn(g, *out.shape))
+    return [out, *torch.autograd.grad(out, [a, b] if a_grad else [b], _randn(g, *out.shape))]
 
 
 def _warp_twice(fn, a_shape, b_shape, both):
@@ -71,7 +89,7 @@ def _warp_twice(fn, a_shape, b_shape, both):
     out = fn(a, b)
     gO = _randn(g, *out.shape, grad=both)
     gb, = torch.autograd.grad(out, b, gO, create_graph=True)
-    torch.autograd.grad(gb, [b, gO] if both else [b], _randn(g, *gb.shape))
+    return [out, gb, *torch.autograd.grad(gb, [b, gO] if both else [b], _randn(g, *gb.shape))]
 
 
 VOX, FLOW = ((2, 6, 5, 7), (2, 3, 5, 7)), ((2, 3, 5, 7), (2, 2, 5, 7))
@@ -97,7 +115,7 @@ def _sepconv_once(frames8, want_gI):
     inp.requires_grad_(want_gI)
     v.requires_grad_(), h.requires_grad_()
     out = S.FunctionSepconv.apply(inp, v, h)
-    torch.autograd.grad(out, ([inp] if want_gI else []) + [v, h], _randn(g, *out.shape))
+    return [out, *torch.autograd.grad(out, ([inp] if want_gI else []) + [v, h], _randn(g, *out.shape))]
 
 
 def _sepconv_twice(frames8):
@@ -107,7 +125,7 @@ def _sepconv_twice(frames8):
     out = S.FunctionSepconvTwice.apply(inp, v, h)
     gO = _randn(g, *out.shape, grad=True)
     gV, gH = torch.autograd.grad(out, [v, h], gO, create_graph=True)
-    torch.autograd.grad([gV, gH], [v, h, gO], [_randn(g, *gV.shape), _randn(g, *gH.shape)])
+    return [out, gV, gH, *torch.autograd.grad([gV, gH], [v, h, gO], [_randn(g, *gV.shape), _randn(g, *gH.shape)])]
 
 
 def _sepconv_pair(frames8=True, one_launch=True):
@@ -117,7 +135,7 @@ def _sepconv_pair(frames8=True, one_launch=True):
     taps = (_randn(g, 4, 51, 4, 8) / 7).requires_grad_()
     with _knob(S, "FRAMES8", frames8), _knob(S, "PAIR_ONE_LAUNCH", one_launch):
         out = S.FunctionSepconvPair.apply(f0, f1, taps)
-        torch.autograd.grad(out, taps, _randn(g, *out.shape))
+        return [out, *torch.autograd.grad(out, taps, _randn(g, *out.shape))]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -127,12 +145,12 @@ def _loss(fn, **kw):
     g = _gen(5)
     sr, hr = _rand(g, 2, 3, 33, 35, grad=True), _rand(g, 2, 3, 33, 35)
     out = fn(sr, hr, **kw)
-    torch.autograd.grad(out, sr, torch.ones_like(out))
+    return [out, *torch.autograd.grad(out, sr, torch.ones_like(out))]
 
 
 def _metric(fn):
     g = _gen(6)
-    fn(_rand(g, 2, 3, 33, 35), _rand(g, 2, 3, 33, 35))
+    return _flat(fn(_rand(g, 2, 3, 33, 35), _rand(g, 2, 3, 33, 35)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -142,9 +160,9 @@ def _fwd_bwd(fn, *shapes, seed=7):
     """fn of seeded leaves of `shapes`, then the gradient of the (first) result for all of them."""
     g = _gen(seed)
     leaves = [_randn(g, *s, grad=True) for s in shapes]
-    out = fn(*leaves)
-    out = out[0] if isinstance(out, (tuple, list)) else out
-    torch.autograd.grad(out, leaves, _randn(g, *out.shape), allow_unused=True)
+    outs = fn(*leaves)
+    out = outs[0] if isinstance(outs, (tuple, list)) else outs
+    return _flat(outs, torch.autograd.grad(out, leaves, _randn(g, *out.shape), allow_unused=True))
 
 
 def _both_outputs(fn, *shapes, seed=8):
@@ -152,7 +170,7 @@ def _both_outputs(fn, *shapes, seed=8):
     g = _gen(seed)
     leaves = [_randn(g, *s, grad=True) for s in shapes]
     a, b = fn(*leaves)
-    torch.autograd.grad([a, b], leaves, [_randn(g, *a.shape), _randn(g, *b.shape)], allow_unused=True)
+    return _flat(a, b, torch.autograd.grad([a, b], leaves, [_randn(g, *a.shape), _randn(g, *b.shape)], allow_unused=True))
 
 
 def _avgpool_second_order():
@@ -160,7 +178,7 @@ def _avgpool_second_order():
     x = _randn(g, 1, 5, 7, 9, grad=True)
     gO = _randn(g, 1, 5, 3, 4, grad=True)
     gx, = torch.autograd.grad(hip_ops.avg_pool2x2(x), x, gO, create_graph=True)
-    torch.autograd.grad(gx, gO, _randn(g, *gx.shape))
+    return [gx, *torch.autograd.grad(gx, gO, _randn(g, *gx.shape))]
 
 
 def _mt_tensors(g, grad=False):
@@ -176,8 +194,9 @@ def _mt_update(rule, lr_mode, lr_grad):
     if rule != _hip.RULE_SGD:
         kw = dict(m=[torch.zeros_like(w) for w in ws], s=[torch.zeros_like(w) for w in ws], bc1=[0.1] * 3, sqrt_bc2=[0.1] * 3)
     outs = hip_ops.mt_update(rule, lr_mode, ws, gs, lrs, **kw)
-    torch.autograd.grad(outs, ws + (lrs if lr_grad else []), [torch.ones_like(o) for o in outs])
+    grads = torch.autograd.grad(outs, ws + (lrs if lr_grad else []), [torch.ones_like(o) for o in outs])
     hip_ops.filters_after_update([])
+    return _flat(outs, grads, kw.get('m'), kw.get('s'))
 
 
 def _mt_update_nograd():
@@ -185,8 +204,9 @@ def _mt_update_nograd():
     ws, gs = _mt_tensors(g)
     lrs = [torch.tensor(0.1, device=DEV) for _ in ws]
     m, s = [torch.zeros_like(w) for w in ws], [torch.zeros_like(w) for w in ws]
-    hip_ops.mt_update_nograd(_hip.RULE_ADAM, _hip.LR_SCALAR, ws, gs, lrs, m, s, [0.1] * 3, [0.1] * 3, 0.9, 0.99, 1e-8, True)
+    res = hip_ops.mt_update_nograd(_hip.RULE_ADAM, _hip.LR_SCALAR, ws, gs, lrs, m, s, [0.1] * 3, [0.1] * 3, 0.9, 0.99, 1e-8, True)
     hip_ops.filters_after_update([])
+    return _flat(res, ws, m, s)
 
 
 def _mt_scale():
@@ -194,19 +214,20 @@ def _mt_scale():
     ws, gs = _mt_tensors(g, grad=True)
     gamma = _rand(g, 3, grad=True)
     outs = hip_ops.mt_scale(gamma, ws)
-    torch.autograd.grad(outs, [gamma] + ws, gs)
-    torch.autograd.grad(hip_ops.mt_scale(gamma, ws)[1], [gamma, ws[1]], gs[1])          # one live output: the compacted gamma
-    hip_ops.mt_scale_grads(gamma, ws, gs)
-    hip_ops.mt_mean(ws)
+    res = [outs, torch.autograd.grad(outs, [gamma] + ws, gs)]
+    res.append(torch.autograd.grad(hip_ops.mt_scale(gamma, ws)[1], [gamma, ws[1]], gs[1]))   # one live output: the compacted gamma
+    res += [hip_ops.mt_scale_grads(gamma, ws, gs), hip_ops.mt_mean(ws)]
     hip_ops.filters_after_update([])
+    return _flat(res)
 
 
 def _mt_copy():
     g = _gen(13)
     srcs, dsts = _mt_tensors(g)
     hip_ops.mt_copy(dsts, srcs)
+    first = [d.clone() for d in dsts]
     hip_ops.MtCopy(dsts, srcs).run()
-    hip_ops.mt_clone(srcs)
+    return _flat(first, dsts, hip_ops.mt_clone(srcs))
 
 
 def _graph_loop_lr_grads():
@@ -214,34 +235,40 @@ def _graph_loop_lr_grads():
     suffix, dirs = _mt_tensors(g)
     rule = types.SimpleNamespace(lr_mode=_hip.LR_SCALAR, names_learning_rates_dict={"w%d" % i: torch.zeros(2) for i in range(3)})
     gl = types.SimpleNamespace(rule=rule, step_out=[{'dir': dirs}], rule_id=_hip.RULE_ADAM, routed=["w0", "w1", "w2"], T=1)
-    graph_inner_loop.OuterGradAccumulator(None, {}).add_lr_grads(gl, 0, suffix)
+    acc = graph_inner_loop.OuterGradAccumulator(None, {})
+    acc.add_lr_grads(gl, 0, suffix)
+    return _flat(acc.lr_rows)
 
 
 def _dain_warp():
     g = _gen(15)
     x, flow, filt = _randn(g, 2, 3, 7, 9, grad=True), (4 * _randn(g, 2, 2, 7, 9)).requires_grad_(), (_randn(g, 2, 16, 7, 9) / 4).requires_grad_()
     out = hip_ops.filter_interpolation(x, flow, filt)
-    torch.autograd.grad(out, [x, flow, filt], _randn(g, *out.shape))
+    grads = torch.autograd.grad(out, [x, flow, filt], _randn(g, *out.shape))
     with torch.no_grad():
-        hip_ops.filter_interpolation_into(torch.zeros(2, 5, 7, 9, device=DEV), 2, x, flow, filt)
+        into = torch.zeros(2, 5, 7, 9, device=DEV)
+        res = hip_ops.filter_interpolation_into(into, 2, x, flow, filt)
+    return _flat(out, grads, into, res)
 
 
 def _dain_projection():
     g = _gen(16)
     flow, wgt = (3 * _randn(g, 2, 2, 7, 9)).requires_grad_(), _rand(g, 2, 1, 7, 9, grad=True)
     out = hip_ops.depth_flow_projection(flow, wgt, 0)
-    torch.autograd.grad(out, [flow, wgt], _randn(g, *out.shape))
-    hip_ops.depth_flow_projection(flow.detach(), wgt.detach(), 1)
+    grads = torch.autograd.grad(out, [flow, wgt], _randn(g, *out.shape))
+    return _flat(out, grads, hip_ops.depth_flow_projection(flow.detach(), wgt.detach(), 1))
 
 
 def _pwc():
     g = _gen(17)
     f1, f2 = _randn(g, 1, 3, 3, 5, grad=True), _randn(g, 1, 3, 3, 5, grad=True)
+    res = []
     for slope in (1.0, 0.1):
         out = hip_ops.correlation(f1, f2, 4, slope)
-        torch.autograd.grad(out, [f1, f2], _randn(g, *out.shape))
+        res += [out, torch.autograd.grad(out, [f1, f2], _randn(g, *out.shape))]
     with torch.no_grad():
-        hip_ops.pwc_warp(_randn(g, 2, 3, 7, 9), 2 * _randn(g, 2, 2, 7, 9), 0.625)
+        res.append(hip_ops.pwc_warp(_randn(g, 2, 3, 7, 9), 2 * _randn(g, 2, 2, 7, 9), 0.625))
+    return _flat(res)
 
 
 def _dain_net():
@@ -249,11 +276,11 @@ def _dain_net():
     with torch.no_grad():
         x = _randn(g, 4, 3, 5, 7)
         mean, var = hip_ops.bn_stats(x, 2)
-        hip_ops.bn_apply_relu(x, mean, var, 2, _rand(g, 3), _randn(g, 3))
-        hip_ops.bn_running_update([torch.zeros(3, device=DEV), torch.ones(3, device=DEV)], [mean[0].contiguous(), var[0].contiguous()], [1.0, 1.5])
-        hip_ops.max_pool2x2(_randn(g, 2, 3, 5, 7))
-        hip_ops.upnearest2x_add(_randn(g, 2, 3, 3, 5), _randn(g, 2, 3, 6, 10))
-    _fwd_bwd(hip_ops.add_relu, (2, 3, 5, 7), (2, 3, 5, 7), seed=19)
+        running = [torch.zeros(3, device=DEV), torch.ones(3, device=DEV)]
+        res = [mean, var, hip_ops.bn_apply_relu(x, mean, var, 2, _rand(g, 3), _randn(g, 3)), x]
+        res.append(hip_ops.bn_running_update(running, [mean[0].contiguous(), var[0].contiguous()], [1.0, 1.5]))
+        res += [running, hip_ops.max_pool2x2(_randn(g, 2, 3, 5, 7)), hip_ops.upnearest2x_add(_randn(g, 2, 3, 3, 5), _randn(g, 2, 3, 6, 10))]
+    return _flat(res, _fwd_bwd(hip_ops.add_relu, (2, 3, 5, 7), (2, 3, 5, 7), seed=19))
 
 
 def _conv_case(name):
@@ -275,8 +302,9 @@ def _conv_case(name):
         else:
             y = hip_ops.conv_bias_act(x, w, b, c["stride"], c["pad"], 1, 1, c["slope"], direct=c["direct"], reflect=c["reflect"],
                                       in_slope=c["in_slope"], defer=c["defer"])
-        torch.autograd.grad(y, ([x] if c["need_x"] else []) + [w] + ([b] if b is not None else []), _randn(g, *y.shape))
+        grads = torch.autograd.grad(y, ([x] if c["need_x"] else []) + [w] + ([b] if b is not None else []), _randn(g, *y.shape))
         hip_ops.join_weight_gradients()
+        return _flat(y, grads)
     finally:
         hip_ops.set_weight_gradient_overlap(False)
 
@@ -289,7 +317,7 @@ def _conv_unit16_cotangent():
     w, b = _randn(g, c["T"], c["Co"], c["Ci"], 3, 3) / 21, _randn(g, c["T"], c["Co"])
     assert hip_ops.conv3x3_in_unit16_supported((c["N"], c["Co"], c["H"] - 2, c["W"] - 2), w, 0)
     y =hip_ops.conv_bias_act_tasks(x, w, b, 1, 0, 1, 1.0, out_unit16=2)
-    torch.autograd.grad(y, x, hip_ops.tag_layout(_randn(g, *y.shape), hip_ops.UNIT16))
+    return _flat(y, torch.autograd.grad(y, x, hip_ops.tag_layout(_randn(g, *y.shape), hip_ops.UNIT16)))
 
 
 def _conv_plain_entries():
@@ -297,23 +325,24 @@ def _conv_plain_entries():
     g = _gen(22)
     x, w, b = _randn(g, 1, 8, 16, 64), _randn(g, 64, 8, 3, 3) / 8, _randn(g, 64)
     y = hip_ops.conv3x3(x, w, b, 0, 0.2, 1)
-    hip_ops.conv3x3(_randn(g, *y.shape), w, None, 1, 1.0, 1)
+    res = [y, hip_ops.conv3x3(_randn(g, *y.shape), w, None, 1, 1.0, 1)]
     xt, wt, bt = _randn(g, 4, 64, 16, 64), _randn(g, 2, 32, 64, 3, 3) / 24, _randn(g, 2, 32)
     for f2 in (False, True):
         yt = hip_ops.conv3x3_tasks(xt, wt, bt, 0, 0.2, 0, f2=f2)
-        hip_ops.conv3x3_tasks(_randn(g, *yt.shape), wt, None, 1, 1.0, 0, f2=f2)
-    hip_ops.conv3x3_wgrad(_randn(g, 1, 32, 16, 64), _randn(g, 1, 32, 16, 64), 1)
+        res += [yt, hip_ops.conv3x3_tasks(_randn(g, *yt.shape), wt, None, 1, 1.0, 0, f2=f2)]
+    res.append(hip_ops.conv3x3_wgrad(_randn(g, 1, 32, 16, 64), _randn(g, 1, 32, 16, 64), 1))
     with _knob(hip_ops, "WGRAD_WINO_MIN_GFLOP", 0.0):
-        hip_ops.conv3x3_wgrad(_randn(g, 2, 32, 16, 16), _randn(g, 2, 32, 16, 16), 1)
-        hip_ops.conv3x3_wgrad_tasks(_randn(g, 2, 20, 37, 53), _randn(g, 2, 70, 37, 53), 2, 1, want_bias=True)
-    hip_ops.conv3x3_wgrad_tasks(_randn(g, 8, 64, 24, 32), _randn(g, 8, 64, 24, 32), 4, 1)
+        res.append(hip_ops.conv3x3_wgrad(_randn(g, 2, 32, 16, 16), _randn(g, 2, 32, 16, 16), 1))
+        res.append(hip_ops.conv3x3_wgrad_tasks(_randn(g, 2, 20, 37, 53), _randn(g, 2, 70, 37, 53), 2, 1, want_bias=True))
+    res.append(hip_ops.conv3x3_wgrad_tasks(_randn(g, 8, 64, 24, 32), _randn(g, 8, 64, 24, 32), 4, 1))
+    return _flat(res)
 
 
 def _conv_pool():
     g = _gen(23)
     x, w, b = _randn(g, 4, 16, 12, 16, grad=True), (_randn(g, 2, 40, 16, 3, 3) / 12).requires_grad_(), _randn(g, 2, 40, grad=True)
     y, pooled = hip_ops.conv_bias_act_tasks_pool(x, w, b, 1, 1, 1, 0.2)
-    torch.autograd.grad([y, pooled], [x, w, b], [_randn(g, *y.shape), _randn(g, *pooled.shape)])
+    return _flat(y, pooled, torch.autograd.grad([y, pooled], [x, w, b], [_randn(g, *y.shape), _randn(g, *pooled.shape)]))
 
 
 def _convk_masked():
@@ -323,33 +352,44 @@ def _convk_masked():
     w = _randn(g, 64, 64, 3, 3) / 24
     _, packed = hip_ops.convk_filters(w, False, True)
     gz, mask = _randn(g, 1, 64, 32, 32), _randn(g, 1, 64, 32, 32)
-    hip_ops.convk_tasks_pre(gz, packed, 1, 64, 64, 3, None, 1, 1.0, 1, mask=mask, mask_slope=0.2)
-    hip_ops.convk_wgrad_tasks(_randn(g, 1, 64, 32, 32), gz, 1, 3, 1, precise=True)
-    hip_ops._filters_multi('convk', [(w, True, True)])
-    hip_ops._filters_multi('wino', [(w, True, False)])
-    hip_ops._filters_multi('wino2', [(w, False, True)])
-    hip_ops.conv3x3_filters(w, True, True, f2=True)
+    res = [packed, hip_ops.convk_tasks_pre(gz, packed, 1, 64, 64, 3, None, 1, 1.0, 1, mask=mask, mask_slope=0.2)]
+    res.append(hip_ops.convk_wgrad_tasks(_randn(g, 1, 64, 32, 32), gz, 1, 3, 1, precise=True))
+    res.append(hip_ops._filters_multi('convk', [(w, True, True)]))
+    res.append(hip_ops._filters_multi('wino', [(w, True, False)]))
+    res.append(hip_ops._filters_multi('wino2', [(w, False, True)]))
+    res.append(hip_ops.conv3x3_filters(w, True, True, f2=True))
+    return _flat(res)
 
 
 def _reflect_pads():
-    _fwd_bwd(lambda x: hip_ops.reflect_pad(x, 2), (1, 3, 7, 9), seed=25)
-    _both_outputs(lambda x: hip_ops.reflect_pad_with_skip(x, 2), (1, 3, 7, 9), seed=26)
+    return (_fwd_bwd(lambda x: hip_ops.reflect_pad(x, 2), (1, 3, 7, 9), seed=25)
+            + _both_outputs(lambda x: hip_ops.reflect_pad_with_skip(x, 2), (1, 3, 7, 9), seed=26))
 
 
 def _upsample():
-    _fwd_bwd(lambda x: hip_ops.upsample_bilinear2x(x, True), (2, 7, 5, 9), seed=27)
-    _fwd_bwd(lambda x: hip_ops.upsample_bilinear2x(x, False, 0.2), (2, 7, 5, 9), seed=28)
-    _fwd_bwd(lambda x: hip_ops.upsample_bilinear2x_window(x, (24, 32), (2, 3), (6, 8, 20, 30), True), (1, 3, 16, 20), seed=29)
-    _fwd_bwd(lambda x: hip_ops.mask_grad(x, 0.2), (2, 3, 5, 7), seed=30)
+    return (_fwd_bwd(lambda x: hip_ops.upsample_bilinear2x(x, True), (2, 7, 5, 9), seed=27)
+            + _fwd_bwd(lambda x: hip_ops.upsample_bilinear2x(x, False, 0.2), (2, 7, 5, 9), seed=28)
+            + _fwd_bwd(lambda x: hip_ops.upsample_bilinear2x_window(x, (24, 32), (2, 3), (6, 8, 20, 30), True), (1, 3, 16, 20), seed=29)
+            + _fwd_bwd(lambda x: hip_ops.mask_grad(x, 0.2), (2, 3, 5, 7), seed=30))
 
 
 def _channel_attention(N, T, C, Cr, H, W):
     shapes = [(N, C, H, W), (N, C, H, W), (T, Cr, C, 1, 1), (T, Cr), (T, C, Cr, 1, 1), (T, C)]
-    _fwd_bwd(hip_ops.channel_attention_residual, *shapes, seed=31)
+    return _fwd_bwd(hip_ops.channel_attention_residual, *shapes, seed=31)
+
+
+def _adacof(grads):
+    """N = 1, C = 3, F = 3, dilation 1, 5x7 outputs (the frame [1,3,7,9]); `grads`: which of w, a, b require grad (the others' gradient
+    pointers go as NULL)."""
+    g = _gen(33)
+    x = _rand(g, 1, 3, 7, 9)
+    w, a, b = (_randn(g, 1, 9, 5, 7, grad=need) for need in grads)
+    out = hip_ops.adacof(x, w, a, b)
+    return _flat(out, torch.autograd.grad(out, [t for t, need in zip((w, a, b), grads) if need], _randn(g, *out.shape)))
 
 
 def _charbonnier(fn):
-    _fwd_bwd(fn, (2, 3, 33, 35), (2, 3, 33, 35), seed=32)
+    return _fwd_bwd(fn, (2, 3, 33, 35), (2, 3, 33, 35), seed=32)
 
 
 CASES = {
@@ -388,12 +428,12 @@ CASES = {
     "psnr_ssim": lambda: _metric(hip_ops.psnr_ssim),
     "psnr_ssim+sq": lambda: _metric(lambda a, b: hip_ops.psnr_ssim(a, b, want_sq_sum=True)),
     "msssim_metric": lambda: _metric(hip_ops.msssim_metric),
-    "frames_to_u8": lambda: hip_ops.frames_to_u8(_rand(_gen(6), 2, 3, 33, 35)),
+    "frames_to_u8": lambda: _flat(hip_ops.frames_to_u8(_rand(_gen(6), 2, 3, 33, 35))),
     "avgpool": lambda: _fwd_bwd(hip_ops.avg_pool2x2, (1, 5, 7, 9)),
     "avgpool-second-order": _avgpool_second_order,
     "avgpool-and-skip": lambda: _both_outputs(lambda x: hip_ops.avg_pool2x2_and_skip(x, 0.2), (2, 5, 12, 16)),
-    "pixel_shuffle": lambda: (_fwd_bwd(lambda x: hip_ops.pixel_shuffle(x, 0.5), (2, 3, 16, 24)),
-                              _fwd_bwd(lambda x: hip_ops.pixel_shuffle(x, 2), (2, 12, 8, 12))),
+    "pixel_shuffle": lambda: (_fwd_bwd(lambda x: hip_ops.pixel_shuffle(x, 0.5), (2, 3, 16, 24))
+                              + _fwd_bwd(lambda x: hip_ops.pixel_shuffle(x, 2), (2, 12, 8, 12))),
     "sub_mean": lambda: _both_outputs(hip_ops.sub_mean, (2, 3, 37, 45)),
     "mt_update-sgd": lambda: _mt_update(_hip.RULE_SGD, _hip.LR_SCALAR, True),
     "mt_update-adam-element": lambda: _mt_update(_hip.RULE_ADAM, _hip.LR_ELEMENT, True),
@@ -413,6 +453,8 @@ CASES = {
     "upsample2x": _upsample,
     "channel-attention-fused": lambda: _channel_attention(3, 3, 16, 2, 5, 7),
     "channel-attention-three-launches": lambda: _channel_attention(2, 1, 320, 20, 8, 8),
+    "adacof": lambda: _adacof((True, True, True)),
+    "adacof-null-grads": lambda: _adacof((True, False, False)),
 }
 CASES.update({"conv-" + name: (lambda name=name: _conv_case(name)) for name in D.CASES})
 
