@@ -87,7 +87,8 @@ extern "C" {
  * the one SepConv route, savfi_sepconv_route, savfi_sepconv_debug_span_bytes; then, for the deep layers' small maps,
  * savfi_convk_wgrad3_small_plan, savfi_convk_wgrad3_small_route, savfi_convk_wgrad3_small_workspace_floats,
  * savfi_convk_wgrad3_small_tasks_f32, savfi_convk_wgrad3_small_tasks_bias_f32; then, for the AdaCoF plugin's deformable-tap op,
- * savfi_adacof_fwd_f32, savfi_adacof_bwd_f32. */
+ * savfi_adacof_fwd_f32, savfi_adacof_bwd_f32; then, for softmax splatting (forward warping), savfi_softsplat_scratch_bytes,
+ * savfi_softsplat_fwd_f32, savfi_softsplat_bwd_f32. */
 #define SAVFI_ABI_VERSION 24
 
 #define SAVFI_OK            0
@@ -549,6 +550,52 @@ int savfi_adacof_fwd_f32(const float* x, const float* w, const float* a, const f
                          int dilation, void* stream);
 int savfi_adacof_bwd_f32(const float* x, const float* w, const float* a, const float* b, const float* g_out, float* g_w, float* g_a,
                          float* g_b, int N, int C, int H, int W, int F, int dilation, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Softmax splatting: forward warping with a learned importance (Niklaus & Liu, CVPR 2020) and its gradients (csrc/softsplat.hip), added
+ * under ABI 24.  This block is the specification; tests/softsplat_ref.py restates it in float64.
+ *   x [N, C, H, W], flow [N, 2, H, W] (channel 0 horizontal, 1 vertical), metric Z [N, 1, H, W] (read in soft mode only; may be NULL
+ *   otherwise), mode 0 = sum, 1 = avg, 2 = soft  ->  out [N, C, H, W], hit, den (D), mx (M) [N, 1, H, W], all four fully overwritten.
+ *   Coordinates.  For the source pixel p = (i, j):  X = float32(j) + flow_x(p),  Y = float32(i) + flow_y(p)  (ONE fp32 addition each: the
+ *   coordinate IS fp32).  x0 = floor(X), tx = X - x0, y0 = floor(Y), ty = Y - y0, all fp32.  The four corners q_k, k = 0 .. 3, are
+ *   (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) with the 1-D factors (1 - tx | tx) and (1 - ty | ty) and the bilinear weight
+ *   b_k their product (factors and everything after them in double).  A corner TAKES PART only if it lies inside the frame and both of its
+ *   1-D factors are > 0 (decided on the factors, not on their product).  All comparisons that keep a coordinate in range are made in float
+ *   before any conversion to an integer.  A source whose flow is non-finite (in soft mode: or whose metric is), or whose target lies
+ *   wholly outside, contributes nothing and receives zero gradients.
+ *   Modes.  sum: out(q) = sum_p b_pq x(p).   avg: out = N / D with e = 1.
+ *   soft: out_c(q) = N_c(q) / D(q),  N_c(q) = sum_p e_pq b_pq x_c(p),  D(q) = sum_p e_pq b_pq,  e_pq = expf(Z_p - M(q)),  M(q) = the
+ *   maximum of Z_p over the sources taking part at q: a true per-target softmax, equal to sum exp(Z) b x / sum exp(Z) b but finite for
+ *   every finite Z (the published implementations overflow above 88).  A `linear` mode is not built: soft with Z = log w expresses it.
+ *   Where nothing lands out = 0, hit = 0, den = 0, mx = 0; elsewhere hit = 1.  den is sum e b in every mode (sum: sum b); mx is 0 outside
+ *   soft mode.  hit carries no gradient.  If a sample of x holds a non-finite element, that whole sample of out is NaN (decided on the
+ *   device; hit, den, mx do not depend on x).
+ *   bwd: ONE launch, a gather per source pixel, no atomics; out, den, mx as the forward left them; g_out [N, C, H, W]; g_x [N, C, H, W],
+ *   g_flow [N, 2, H, W], g_metric [N, 1, H, W], each fully overwritten, each may be NULL ("not wanted"), but not all three.
+ *     s_k = sum_c g_c(q_k) (x_c(p) - out_c(q_k)) / D(q_k)            (sum mode: s_k = sum_c g_c(q_k) x_c(p), D = 1)
+ *     g_x_c(p) = sum_k e_k b_k g_c(q_k) / D(q_k)       g_Z(p) = sum_k s_k e_k b_k       g_flow(p) = sum_k s_k e_k d b_k / d(X, Y)
+ *   M is a constant (exact: out does not depend on it); a corner that did not take part contributes 0; g_metric is 0 outside soft mode.
+ *   Errors, checked in this order before any launch: SAVFI_E_NULL (a required pointer; in bwd all three gradient outputs);
+ *   SAVFI_E_SHAPE (one of N, C, H, W <= 0); SAVFI_E_UNSUPPORTED (C above 256, an unknown mode, soft mode without a metric, an output
+ *   pointer equal to an operand or to another output, a float pointer that is not 4-byte aligned or a scratch that is not 8-byte
+ *   aligned); SAVFI_E_TOOBIG (H W > 2^31 - 1 - 256, N > 65535 or N (C + 1) H W >= 2^40).  savfi_softsplat_scratch_bytes returns the same
+ *   codes for its numbers.
+ *   Forward, four launches: init (our own kernel, never a memset: a captured memset node clears only once), scan (per-sample maximum of
+ *   |x| as an integer maximum of the bit patterns -> a power-of-two scale; the non-finite flag; in soft mode the scatter-max of Z onto the
+ *   corners taking part, an integer maximum of an order-preserving key), scatter (one thread per source pixel and channel chunk;
+ *   contributions formed in double, converted to 64-bit fixed point, rounded away from zero, added with 64-bit integer atomics: the
+ *   denominator under the constant scale 2^(62 - ceil(log2(H W))) -- each share is at most 1 and at most H W reach a target -- the
+ *   numerators under that scale divided by the power of two above the sample's largest |x|), finish.  No float atomics, no host read, no
+ *   memset node: capturable and bit-reproducible, and each sample depends on itself alone.  expf, IEEE division, no contraction.
+ *   `scratch`: savfi_softsplat_scratch_bytes(N, C, H, W) bytes, 8-byte aligned, caller-owned: int64 acc[N][C + 1][H W], uint32
+ *   keys[N][H W], uint32 words[N][2], the total rounded up to a multiple of 16.
+ * ---------------------------------------------------------------------------------- */
+int64_t savfi_softsplat_scratch_bytes(int N, int C, int H, int W);
+int savfi_softsplat_fwd_f32(const float* x, const float* flow, const float* metric, float* out, float* hit, float* den, float* mx,
+                            void* scratch, int N, int C, int H, int W, int mode, void* stream);
+int savfi_softsplat_bwd_f32(const float* x, const float* flow, const float* metric, const float* out, const float* den, const float* mx,
+                            const float* g_out, float* g_x, float* g_flow, float* g_metric, int N, int C, int H, int W, int mode,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution epilogue: bias + activation, in place on the conv output z [N,C,H*W]:

@@ -18,6 +18,7 @@ RULE_SGD, RULE_ADAM, RULE_ADAMAX_LSLR, RULE_ADAMAX_MSGD = 0, 1, 2, 3
 LR_SCALAR, LR_ELEMENT = 0, 1
 SSIM_RANGE_PER_ROW, SSIM_RANGE_BATCH, SSIM_RANGE_FIXED = 0, 1, 2
 SEPCONV_PARTITION_WS, SEPCONV_PARTITION_X6, SEPCONV_PARTITION_FP32 = 0, 1, 2
+SOFTSPLAT_MODES = {'sum': 0, 'avg': 1, 'soft': 2}
 SEPCONV_ROUTE_DIRECT = 3                  # savfi_sepconv_route: the direct kernels (the three above: the persistent ones)
 ABI_VERSION = 24
 
@@ -96,6 +97,9 @@ _PROTOTYPES = {
     "savfi_census_bwd_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "savfi_adacof_fwd_f32": [_P] * 5 + [c_int] * 6 + [_P],
     "savfi_adacof_bwd_f32": [_P] * 8 + [c_int] * 6 + [_P],
+    "savfi_softsplat_scratch_bytes": [c_int] * 4,
+    "savfi_softsplat_fwd_f32": [_P] * 8 + [c_int] * 5 + [_P],
+    "savfi_softsplat_bwd_f32": [_P] * 10 + [c_int] * 5 + [_P],
     "savfi_upsample2x_fwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_upsample2x_bwd_f32": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "savfi_conv3x3_workspace_floats": [c_int] * 7,

@@ -28,6 +28,10 @@ Additions for the MI355X build (all optional, all default to the reference behav
                                second-order passes
   --adacof_kernel_size F       --model adacof: F x F taps per output pixel, each with a weight and a learned 2-D offset (odd, 1 to 11; default 5)
   --adacof_dilation D          --model adacof: spacing of the taps' base positions (1 to 8; default 1); the op reads a frame padded by (F - 1) D / 2
+  --softsplat_alpha A          --model softsplat: the initial value of the learnable scalar that turns the backward-warp photometric error into the
+                               splatting metric, Z = A * mean_c |I0 - warp(I1, F_0_1)| (default -20: a badly matching source gives way)
+  --softsplat_mode {soft,avg}  --model softsplat: soft weights colliding sources by exp(Z) as a per-target softmax (default); avg averages them
+                               with their bilinear shares alone (no metric is formed)
   --loss ...+w*MSSSIM          a term the reference's Loss has no branch for: 1 - msssim(sr, hr, normalize=True) on the fused multi-scale kernels
   --loss ...+w*Lap             another one: the Laplacian-pyramid L1 (five levels, 5-tap binomial window, reflected borders, low-pass residual last,
                                sum_s 2^s sum |b_s| / n_0) on the fused kernels of csrc/laploss.hip; frames of 17 x 17 or more
@@ -71,12 +75,13 @@ _FLAGS = {
         ('task_streams', int, -1), ('wgrad_overlap', int, 0), ('task_batch', int, 8), ('lazy_logging', int, 1),
         ('dain_task_modes', int, 0), ('eval_msssim', int, 0), ('sepconv_second_order', int, 0),
         ('warp_second_order', int, 0), ('adacof_kernel_size', int, 5), ('adacof_dilation', int, 1),
+        ('softsplat_alpha', float, -20.0), ('softsplat_mode', str, 'soft'),
         ('synthetic', 'flag', False),
     ],
 }
 
 _CHOICES = {'mode': ['train', 'val', 'test'], 'eval_msssim': [0, 1], 'sepconv_second_order': [0, 1], 'warp_second_order': [0, 1],
-            'adacof_kernel_size': [1, 3, 5, 7, 9, 11], 'adacof_dilation': list(range(1, 9))}
+            'adacof_kernel_size': [1, 3, 5, 7, 9, 11], 'adacof_dilation': list(range(1, 9)), 'softsplat_mode': ['soft', 'avg']}
 
 
 def build_parser():

@@ -1333,6 +1333,151 @@ def adacof(x, w, a, b, dilation=1):
     return _AdaCoF.apply(x, w, a, b, F, int(dilation))
 
 
+# --------------------------------------------------------------------------------------------
+# Softmax splatting (forward warping), the op of --model softsplat   (no counterpart in the reference; definition: include/savfi_hip.h)
+# --------------------------------------------------------------------------------------------
+SOFTSPLAT_MODES = _hip.SOFTSPLAT_MODES
+
+
+def softsplat_bytes(x, mode='soft', grads=0):
+    """Algorithmic HBM bytes of one call if every operand moves once per launch that touches it.  Forward (grads=0): x twice (scan,
+    scatter), flow and metric twice in soft mode (once otherwise), the C + 1 64-bit accumulators cleared, added to and read, the keys
+    likewise, out + hit + D + M written.  Backward (grads = number of gradient tensors wanted, each counted at the size of the mean of
+    the three): x, out, g_out, flow, metric, D, M read, the gradients written."""
+    N, C, H, W = x.shape
+    px, soft = N * H * W, mode == 'soft'
+    if not grads:
+        return px * (8 * C + (2 if soft else 1) * (8 + (4 if soft else 0)) + 3 * 8 * (C + 1) + 3 * 4 + 4 * C + 12)
+    return px * (12 * C + 8 + (4 if soft else 0) + 8 + grads * (4 * C + 12) // 3)
+
+
+class _SoftSplat(torch.autograd.Function):
+    """x [N,C,H,W], flow [N,2,H,W], metric [N,1,H,W] or None -> out [N,C,H,W], hit [N,1,H,W] (no gradient): four launches forward, one
+    backward for whichever of the three gradients are needed; capturable; bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, flow, metric, mode):
+        _hip.require_cuda(x, flow, metric)
+        N, C, H, W = x.shape
+        out = torch.empty_like(x)
+        hit, den, mx = (torch.empty((N, 1, H, W), dtype=x.dtype, device=x.device) for _ in range(3))
+        scratch = torch.empty(_workspace_floats("savfi_softsplat_scratch_bytes", N, C, H, W), dtype=torch.uint8, device=x.device)
+        _hip.call("softsplat_fwd", "savfi_softsplat_fwd_f32", x, flow, metric, out, hit, den, mx, scratch, N, C, H, W, SOFTSPLAT_MODES[mode],
+                  nbytes=softsplat_bytes(x, mode))
+        ctx.mode = mode
+        ctx.has_metric = metric is not None
+        ctx.save_for_backward(*((x, flow, out, den, mx) + ((metric,) if metric is not None else ())))
+        ctx.mark_non_differentiable(hit)
+        return out, hit
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _ghit):
+        x, flow, out, den, mx = ctx.saved_tensors[:5]
+        metric = ctx.saved_tensors[5] if ctx.has_metric else None
+        needs = ctx.needs_input_grad[:3]
+        if not any(needs):
+            return None, None, None, None
+        g = g.contiguous()
+        _hip.require_cuda(g)
+        N, C, H, W = x.shape
+        gx = torch.empty_like(x) if needs[0] else None
+        gf = torch.empty_like(flow) if needs[1] else None
+        gm = torch.empty_like(metric) if needs[2] else None
+        _hip.call("softsplat_bwd", "savfi_softsplat_bwd_f32", x, flow, metric, out, den, mx, g, gx, gf, gm, N, C, H, W,
+                  SOFTSPLAT_MODES[ctx.mode], nbytes=softsplat_bytes(x, ctx.mode, sum(needs)))
+        return gx, gf, gm, None
+
+
+def _softsplat_args(x, flow, metric, mode, what):
+    """The checks of the C entry that shapes decide (a ValueError names the argument instead of an error code) -> the metric the mode reads"""
+    if mode not in SOFTSPLAT_MODES:
+        raise ValueError("%s: mode must be one of %s, got %r (a linear mode is soft with metric = log w)" % (what, sorted(SOFTSPLAT_MODES), mode))
+    if x.dim() != 4 or flow.dim() != 4 or flow.shape != (x.shape[0], 2, x.shape[2], x.shape[3]):
+        raise ValueError("%s needs x [N,C,H,W] and flow [N,2,H,W], got %s, %s" % (what, tuple(x.shape), tuple(flow.shape)))
+    if x.shape[1] > 256 or 0 in x.shape:
+        raise ValueError("%s needs 1 to 256 channels and a non-empty tensor, got %s" % (what, tuple(x.shape)))
+    if mode != 'soft':
+        return None                      # sum and avg read no metric
+    if metric is None:
+        raise ValueError("%s: mode 'soft' needs a metric [N,1,H,W]" % what)
+    if metric.shape != (x.shape[0], 1, x.shape[2], x.shape[3]):
+        raise ValueError("%s needs a metric [N,1,H,W] for x %s, got %s" % (what, tuple(x.shape), tuple(metric.shape)))
+    return metric
+
+
+def softsplat_composed(x, flow, metric=None, mode='soft', return_hit=False):
+    """The definition of softsplat() from differentiable torch ops, on any device and in any floating dtype: what second-order passes
+    (set_double_backward(True)), CPU tensors and non-fp32 tensors take.  The coordinate is formed in the tensors' dtype (one addition to an
+    exact integer); the sums are index_add scatters (on a device: float atomics, not bit-reproducible), M is a scatter_reduce(amax) of
+    detached values; differentiable to any order in x, flow and metric."""
+    metric = _softsplat_args(x, flow, metric, mode, "softsplat_composed")
+    N, C, H, W = x.shape
+    dt, dev, hw = x.dtype, x.device, H * W
+    X = torch.arange(W, device=dev, dtype=dt).view(1, 1, W) + flow[:, 0]
+    Y = torch.arange(H, device=dev, dtype=dt).view(1, H, 1) + flow[:, 1]
+    src = (X > -1) & (X < W) & (Y > -1) & (Y < H)                   # NaN, +-inf and 1e30 fail; what any corner taking part needs
+    if metric is not None:
+        src = src & torch.isfinite(metric[:, 0])
+    zero = torch.zeros((), dtype=dt, device=dev)
+    X, Y = torch.where(src, X, zero), torch.where(src, Y, zero)     # a source taking no part: finite stand-ins, masked out below
+    x0, y0 = X.detach().floor(), Y.detach().floor()
+    tx, ty = X - x0, Y - y0
+    wx, wy = (1 - tx, tx), (1 - ty, ty)
+    base = (torch.arange(N, device=dev) * hw).view(N, 1, 1)
+    idx, ok, b = [], [], []
+    for k in range(4):
+        dx, dy = k & 1, k >> 1
+        xx, yy = x0 + dx, y0 + dy
+        take = src & (xx >= 0) & (xx <= W - 1) & (yy >= 0) & (yy <= H - 1) & (wx[dx].detach() > 0) & (wy[dy].detach() > 0)
+        ok.append(take)
+        idx.append((base + torch.where(take, yy * W + xx, zero).long()).reshape(-1))
+        b.append(torch.where(take, wx[dx] * wy[dy], zero).reshape(-1))
+    if metric is not None:
+        Z = torch.where(src, metric[:, 0], zero).reshape(-1)
+        low = torch.full((), float('-inf'), dtype=dt, device=dev)
+        M = torch.full((N * hw,), float('-inf'), dtype=dt, device=dev)
+        for k in range(4):
+            M = M.scatter_reduce(0, idx[k], torch.where(ok[k].reshape(-1), Z.detach(), low), 'amax', include_self=True)
+        w = [b[k] * torch.exp(Z - torch.where(ok[k].reshape(-1), M[idx[k]], Z.detach())) for k in range(4)]
+    else:
+        w = b
+    xs = x.permute(0, 2, 3, 1).reshape(N * hw, C)
+    num = torch.zeros((N * hw, C), dtype=dt, device=dev)
+    den = torch.zeros((N * hw,), dtype=dt, device=dev)
+    cnt = torch.zeros((N * hw,), dtype=dt, device=dev)
+    for k in range(4):
+        num = num.index_add(0, idx[k], w[k].unsqueeze(1) * xs)
+        den = den.index_add(0, idx[k], w[k])
+        cnt = cnt.index_add(0, idx[k], ok[k].reshape(-1).to(dt))
+    hit = cnt > 0
+    if mode == 'sum':
+        out = num
+    else:
+        out = torch.where(hit.unsqueeze(1), num / torch.where(hit, den, torch.ones((), dtype=dt, device=dev)).unsqueeze(1), zero)
+    out = out.reshape(N, H, W, C).permute(0, 3, 1, 2)
+    bad = ~torch.isfinite(x.detach()).flatten(1).all(1)
+    out = torch.where(bad.view(N, 1, 1, 1), torch.full((), float('nan'), dtype=dt, device=dev), out).contiguous()
+    return (out, hit.reshape(N, 1, H, W).to(dt)) if return_hit else out
+
+
+def softsplat(x, flow, metric=None, mode='soft', return_hit=False):
+    """Softmax splatting (forward warping): the source pixel p of x [N,C,H,W] lands at p + flow(p) (flow [N,2,H,W], x then y) and is shared
+    bilinearly among the four pixels around it.  mode 'sum': the plain sum of the shares; 'avg': divided by the sum of the weights;
+    'soft': weighted by exp(metric) [N,1,H,W] as a per-target softmax, finite for every finite metric (include/savfi_hip.h).  Where
+    nothing lands the result is 0; return_hit: also hit [N,1,H,W], 1 where something landed (no gradient).  fp32 device tensors take the
+    fused kernels (four launches forward, one backward; gradients for x, flow and metric; bit-reproducible).  Second-order passes, CPU
+    tensors and other dtypes take softsplat_composed."""
+    metric = _softsplat_args(x, flow, metric, mode, "softsplat")
+    tensors = (x, flow) + (() if metric is None else (metric,))
+    if double_backward() or not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return softsplat_composed(x, flow, metric, mode, return_hit)
+    x, flow = x.contiguous(), flow.contiguous()
+    metric = None if metric is None else metric.contiguous()
+    out, hit = _SoftSplat.apply(x, flow, metric, mode)
+    return (out, hit) if return_hit else out
+
+
 def frames_to_u8(x):
     """x [N,C,H,W] (or [C,H,W], [H,W]) in unit range, C = 1 or 3 -> uint8 [N,H,W,C] ([H,W,C], [H,W]) on the device, quantised as
     utils.save_image does (the metric's device function): a frame leaves the device as bytes."""

@@ -8,7 +8,12 @@ RCCL all-reduce of outer gradients per iteration; with a single process it is th
 
 --model adacof (an addition: the reference has no such plugin) is the SepConv U-Net with AdaCoF's deformable-tap tail on fused HIP kernels
 (adacof/model.py; --adacof_kernel_size, --adacof_dilation); every task mode of the SepConv plugin applies, --second_order and the host take
-the op composed from torch ops."""
+the op composed from torch ops.
+
+--model softsplat (another addition) forward-warps both frames to the time stamp with softmax splatting on fused HIP kernels
+(softsplat/model.py; --softsplat_alpha, --softsplat_mode) between Super SloMo's flow U-Net and a refinement U-Net; a
+pretrained_models/softsplat_base.pth is loaded as adacof_base.pth is (no public checkpoint was on hand: not verified); every task mode
+applies, --second_order takes the op composed from torch ops and needs --warp_second_order 1 for the metric's backward warp."""
 from .config import get_args
 from .data import MetaLearningSystemDataLoader
 from .experiment_builder import ExperimentBuilder

@@ -83,8 +83,13 @@ def _build_adacof(args, resume):
                       resume=resume)
 
 
+def _build_softsplat(args, resume):
+    from .softsplat.model import MetaSoftSplat
+    return MetaSoftSplat(alpha=float(getattr(args, 'softsplat_alpha', -20.0)), mode=str(getattr(args, 'softsplat_mode', 'soft')), resume=resume)
+
+
 MODEL_REGISTRY = {'sepconv': _build_sepconv, 'cain': _build_cain, 'voxelflow': _build_voxelflow, 'rrin': _build_rrin,
-                  'superslomo': _build_superslomo, 'dain': _build_dain, 'adacof': _build_adacof}
+                  'superslomo': _build_superslomo, 'dain': _build_dain, 'adacof': _build_adacof, 'softsplat': _build_softsplat}
 
 
 def register_model(name, factory):

@@ -13,7 +13,8 @@ import torch
 
 # Xavier-uniform bound multiplier per plugin: keeps un-normalised random nets at O(1) outputs
 # (raw Xavier makes CAIN's 127-conv stack blow up to L1 ~ 20; SepConv's separable taps need 1.2x to leave ~0).
-_GAIN = {'sepconv': 1.2, 'cain': 0.5, 'voxelflow': 1.0, 'rrin': 1.0, 'superslomo': 1.68, 'adacof': 1.2}
+_GAIN = {'sepconv': 1.2, 'cain': 0.5, 'voxelflow': 1.0, 'rrin': 1.0, 'superslomo': 1.68, 'adacof': 1.2,
+         'softsplat': 1.4}
 # per sub-network overrides (name prefix): RRIN's flow nets need > 1 to produce flows of a sizeable fraction of a pixel,
 # its `final` residual net < 1 so that the clamp(0, 1) at the end does not saturate
 _GAIN_PREFIX = {'rrin': {'Flow_L.': 1.3, 'refine_flow.': 1.3, 'final.': 0.85},
@@ -24,7 +25,16 @@ _GAIN_PREFIX = {'rrin': {'Flow_L.': 1.3, 'refine_flow.': 1.3, 'final.': 0.85},
                 # mean of texels cannot leave the frame's range).  1.6 gives mean 0.22 / largest 1.6, 2.0 mean 0.53 / largest 3.9: the
                 # middle one is taken -- no larger than the two paths need: every cell an offset crosses is a kink an inner step can move
                 # over, which is what makes the VoxelFlow default recipe chaotic
-                'adacof': {'moduleAlpha': 1.8, 'moduleBeta': 1.8}}
+                'adacof': {'moduleAlpha': 1.8, 'moduleBeta': 1.8},
+                # softsplat: 1.4 for the flow U-Net, 1.0 for the refinement U-Net (its residual must not drown the splats).  The frames
+                # are unit range, not mean-subtracted, so Super SloMo's 1.68 gives this flow U-Net a rough field of mean |flow| 2.9 px,
+                # up to 14.7 px, on the seeded 128 x 128 septuplet: the forward warp of such a field is a scramble, and in float64 a
+                # relative weight perturbation of 1e-7 moves a gradient fingerprint by 2.3e-5 of its abs-sum (230-fold).  1.4 gives mean
+                # 0.26 px, up to 1.2 px -- sources stay in their cell and cross it, collide and leave the frame at its border -- and the
+                # same perturbation moves 2.3e-7 (2-fold); 1.2 gives mean 0.06 px.  No larger than the paths of the op need
+                'softsplat': {'refine.': 1.0}}
+# tensors the seeded recipe leaves at the module's own initial value (name -> nothing to draw): softsplat's metric scale --softsplat_alpha
+_KEEP = {'softsplat': ('alpha',)}
 # Super SloMo works on mean-subtracted frames (data/vimeo_septuplet.py:31-33; meta_learning_system.py:71-73 undoes it)
 SUPERSLOMO_MEAN = (0.429, 0.431, 0.397)
 
@@ -50,7 +60,9 @@ def seeded_state_dict(net, model, seed=12345, recipe=None):
                 gain = g
         rs = _stream(seed, name)
         shape = tuple(ref.shape)
-        if name.endswith('num_batches_tracked'):
+        if name in _KEEP.get(model, ()):
+            val = ref.detach().cpu().numpy()
+        elif name.endswith('num_batches_tracked'):
             val = np.zeros(shape, dtype=np.int64)
         elif name.endswith('running_mean'):
             val = rs.uniform(-0.1, 0.1, size=shape)
