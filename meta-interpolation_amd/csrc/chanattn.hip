@@ -74,7 +74,8 @@ __global__ __launch_bounds__(CA_T) void ca_mlp_fwd_kernel(const float* __restric
     for (int c = threadIdx.x; c < C; c += CA_T) p += W1[(size_t)j * C + c] * sn[c];
     const float z = block_sum<CA_T / SAVFI_WAVE>(p, red);
     if (threadIdx.x == 0) {
-      const float h = fmaxf(z + b1[t * Cr + j], 0.f);
+      const float zb = z + b1[t * Cr + j];
+      const float h = zb <= 0.f ? 0.f : zb;             // relu that keeps NaN, as torch's does
       hid[j] = h;
       a1[(size_t)n * Cr + j] = h;
     }
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(CA_T) void ca_mlp_bwd_kernel(const float* __restric
       for (int c = threadIdx.x; c < C; c += CA_T, ++k) p += W2[(size_t)c * Cr + j] * dz2[k];
       const float da = block_sum<CA_T / SAVFI_WAVE>(p, red);
       if (threadIdx.x == 0) {
-        const float d = a1s[j] > 0.f ? da : 0.f;
+        const float d = a1s[j] <= 0.f ? 0.f : da;          // torch's threshold backward: a NaN activation passes da
         dz1s[j] = d;
         gb1[t * Cr + j] += d;
       }
@@ -186,7 +187,8 @@ __global__ __launch_bounds__(CA_T) void ca_mlp_fwd_small(const float* __restrict
   for (int j = 0; j < CRM; ++j) p[j] = (j < Cr && c < C) ? W1[(size_t)j * C + c] * sv : 0.f;
   ca_block_sums(p, Cr, red, hid);
   if (c < Cr) {
-    const float h = fmaxf(hid[c] + b1[t * Cr + c], 0.f);
+    const float zb = hid[c] + b1[t * Cr + c];
+    const float h = zb <= 0.f ? 0.f : zb;               // relu that keeps NaN, as torch's does
     a1[(size_t)n * Cr + c] = h;
     hid[c] = h;
   }
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(CA_T) void ca_mlp_bwd_small(const float* __restrict
     for (int j = 0; j < CRM; ++j) p[j] = w2r[j] * dz2;
     ca_block_sums(p, Cr, red, da);            // also publishes a1s (barrier inside)
     if (c < Cr) {
-      const float d = a1s[c] > 0.f ? da[c] : 0.f;
+      const float d = a1s[c] <= 0.f ? 0.f : da[c];       // torch's threshold backward: a NaN activation passes da
       dz1s[c] = d;
       g_b1 += d;
     }
@@ -299,7 +301,8 @@ __global__ __launch_bounds__(CA_T) void ca_apply_mlp_kernel(const float* __restr
   for (int j = 0; j < CRM; ++j) p[j] = (j < Cr && c < C) ? W1[(size_t)j * C + c] * sv : 0.f;
   ca_block_sums(p, Cr, red, hid);
   if (c < Cr) {
-    const float h = fmaxf(hid[c] + b1[t * Cr + c], 0.f);
+    const float zb = hid[c] + b1[t * Cr + c];
+    const float h = zb <= 0.f ? 0.f : zb;               // relu that keeps NaN, as torch's does
     if (cch == 0 && chunk == 0) a1[(size_t)n * Cr + c] = h;
     hid[c] = h;
   }
@@ -364,7 +367,7 @@ __global__ __launch_bounds__(CA_T) void ca_apply_bwd_mlp_kernel(const float* __r
       for (int j = 0; j < CRM; ++j) p[j] = w2r[j] * dz2;
       ca_block_sums(p, Cr, red, da);
       if (c < Cr) {
-        const float d = a1s[c] > 0.f ? da[c] : 0.f;
+        const float d = a1s[c] <= 0.f ? 0.f : da[c];       // torch's threshold backward: a NaN activation passes da
         dz1s[c] = d;
         g_b1 += d;
       }
@@ -404,7 +407,7 @@ __global__ __launch_bounds__(CA_T) void ca_apply_bwd_mlp_kernel(const float* __r
   ca_block_sums(p, Cr, red, da);            // also publishes a1s (barrier inside)
   if (c == cch) {
     float v = 0.f;
-    for (int j = 0; j < Cr; ++j) v += W1[(size_t)j * C + c] * (a1s[j] > 0.f ? da[j] : 0.f);
+    for (int j = 0; j < Cr; ++j) v += W1[(size_t)j * C + c] * (a1s[j] <= 0.f ? 0.f : da[j]);
     dsh = v * inv_hw;
   }
   __syncthreads();

@@ -591,8 +591,8 @@ __global__ __launch_bounds__(WNT, 2) void wino_conv3x3(WinoArgs a) {
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         float v0 = y[r][0] + b, v1 = y[r][1] + b;
-        v0 = fmaxf(v0, 0.f) + slope * fminf(v0, 0.f);      // v > 0 ? v : slope * v
-        v1 = fmaxf(v1, 0.f) + slope * fminf(v1, 0.f);
+        v0 = v0 > 0.f ? v0 : fmaf(slope, v0, 0.f);         // keeps NaN (fmaxf / fminf would drop it); + 0: slope 0 gives +0, as before
+        v1 = v1 > 0.f ? v1 : fmaf(slope, v1, 0.f);
         if (masked) {
           v0 = mk[cb][rep][r].x > 0.f ? v0 : v0 * a.mask_slope;
           v1 = mk[cb][rep][r].y > 0.f ? v1 : v1 * a.mask_slope;

@@ -642,7 +642,8 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
   auto store = [&](auto cb_tag, const f32x2 (&t4)[4][6]) {
     constexpr int cb = decltype(cb_tag)::value;
     // ACT (wave-uniform, one branch per round): 0 = nothing to add (a data gradient), 1 = bias, 2 = bias + ReLU, 3 = bias + leaky ReLU --
-    // 1 / 2 / 4 instead of 4 VALU per output element
+    // 1 / 3 / 4 VALU per output element (add; add, compare, select; add, fma, compare, select).  Both activations keep NaN, and give
+    // fmaxf(v, 0) + slope * fminf(v, 0) bit for bit on every finite v: the zeros they produce are +0 (`<=`, and the fma's `+ 0`)
     auto finish = [&](auto act_tag) {
       constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
@@ -662,8 +663,8 @@ __global__ __launch_bounds__(256, 2) void wino4_conv3x3(W4Args a) {
           for (int c = 0; c < 4; ++c) {
             float v = y[c];
             if constexpr (ACT >= 1) v += b;
-            if constexpr (ACT == 2) v = fmaxf(v, 0.f);
-            if constexpr (ACT == 3) v = fmaxf(v, 0.f) + slope * fminf(v, 0.f);
+            if constexpr (ACT == 2) v = v <= 0.f ? 0.f : v;                // keeps NaN, as torch's relu does (fmaxf would drop it)
+            if constexpr (ACT == 3) v = v > 0.f ? v : fmaf(slope, v, 0.f);
             if constexpr (MASK) v = mk[MASK ? ch : 0][r][c] > 0.f ? v : v * a.mask_slope;
             y[c] = v;
           }

@@ -100,6 +100,11 @@ def pool7(mag):
     return F.max_pool2d(mag, 7, stride=1, padding=3)
 
 
+def local_bound(mag, c_family):
+    """the local gate as a per-element bound: c_family * 2^-24 * L"""
+    return c_family * ULP * mag
+
+
 def local_ratio(got, ref, mag):
     """max over elements of |got - ref| / (2^-24 L): the measured constant of the local gate (0 where L = 0 and got == ref)."""
     d = (got.double() - ref).abs()
